@@ -120,10 +120,44 @@ def spawn_ranks(n: int) -> int:
     return rc
 
 
-def step_bench(arch, n_in, n_cls, size, batch, dtype, steps, warmup, rank, world, dev, log, probe=True, use_graph=False, self_attention=False):
+DUMP_SAMPLE = 1 << 21      # elements kept of each large output by --dump-outputs (8 MB of float32 apiece)
+
+
+def _sample(t: torch.Tensor, seed: int):
+    """t flattened, or a fixed seeded sample of DUMP_SAMPLE of its elements (sorted positions, drawn on the host) when it is larger"""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(d: Path, model, loss, log):
+    """--dump-outputs: what the timed train step computed in its last step, as float .npy files (about 25 MB in all) -- the loss it
+    returns, the logits of its forward (NCHW order), and the parameters, their gradients and the floating-point buffers (BatchNorm
+    running statistics) it left in the model, in model order (independent of the flat-buffer layout)"""
+    import numpy as np
+    d.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    params = list(model.parameters())
+    arrays = {
+        "loss": loss.detach().double().reshape(-1).cpu().numpy(),
+        "logits": _sample(model.logits_ts().view().permute(0, 3, 1, 2), 1),
+        "params": _sample(torch.cat([p.detach().reshape(-1) for p in params]), 2),
+        "grads": _sample(torch.cat([p.grad.reshape(-1) for p in params]), 2),
+        "buffers": _sample(torch.cat([b.reshape(-1) for b in model.buffers() if b.is_floating_point()]), 3),
+    }
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+    log(f"dump-outputs: {', '.join(f'{k} {v.shape}' for k, v in arrays.items())} -> {d}")
+
+
+def step_bench(arch, n_in, n_cls, size, batch, dtype, steps, warmup, rank, world, dev, log, probe=True, use_graph=False, self_attention=False,
+               dump_dir=None):
     """K timed fwd + weighted-CE + bwd + fastai-Adam steps on `batch` synthetic tiles per GPU.  Returns the measurements of this rank
     (wall time of the K steps bracketed by barrier + synchronize, dominant-kernel probe, time the compute stream waited for the gradient
-    all-reduce)."""
+    all-reduce).  dump_dir: rank 0 writes the outputs of the last timed step there (dump_outputs)."""
     from unet_amd import ops as _ops
     from unet_amd.distributed import broadcast_parameters
     from unet_amd.model import HipDynamicUnet
@@ -170,6 +204,8 @@ def step_bench(arch, n_in, n_cls, size, batch, dtype, steps, warmup, rank, world
     wait_ms = None
     if step.comm_events:
         wait_ms = sum(a.elapsed_time(b) for a, b in step.comm_events) / steps
+    if dump_dir is not None and rank == 0:
+        dump_outputs(Path(dump_dir), model, loss, log)
     out = {"dt": dt, "t_local": t_local, "loss": float(loss.item()), "probe": None if pr is None else pr.summary(),
            "mem": model.memory_bytes(), "allreduce_wait_ms": wait_ms}
     del step, opt, model
@@ -492,7 +528,11 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (bf16 step, predict, cfg1, cfg5) of the N=1 run")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
                     help="f32 (default): the parity path, the headline.  bf16: bf16 storage / fp32 accumulate variant of configs[1]")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the headline step computed in its last step to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))          # this process never initialises the GPU
@@ -513,7 +553,8 @@ def main():
         if rank == 0:
             print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
-    res = step_bench(ARCH, N_IN, N_CLS, SIZE, args.batch, args.dtype, args.steps, args.warmup, rank, world, dev, log)
+    res = step_bench(ARCH, N_IN, N_CLS, SIZE, args.batch, args.dtype, args.steps, args.warmup, rank, world, dev, log,
+                     dump_dir=args.dump_outputs)
     dt = res["dt"]
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)

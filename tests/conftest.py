@@ -20,6 +20,16 @@ def pytest_configure(config):
         pass
 
 
+@pytest.fixture(autouse=True)
+def _default_tuning():
+    """kernel-selection switches a test sets (ops.set_knob / ops.set_tuning) end with it: tests that put a switch back to its default value
+    still leave a tuning struct behind, and the next test in the same process would not start from the library defaults"""
+    yield
+    ops = sys.modules.get("unet_amd.ops")      # (looked up, not imported: importing it loads the HIP library)
+    if ops is not None:
+        ops.set_tuning()
+
+
 def pytest_collection_modifyitems(config, items):
     """GPU tests are skipped (not failed) when no GPU is visible and `-m gpu` was not requested."""
     try:
