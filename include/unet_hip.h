@@ -320,6 +320,19 @@ int unet_focal_fwd(const float* z, int z_cs, int z_co, const int64_t* target, co
                    float* loss /*[1]*/, float* workspace, void* stream);
 int unet_focal_bwd(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C, float gamma,
                    float gscale, float* dz, int dz_cs, int dz_co, void* stream);
+/* DiceLoss(axis=1, smooth, reduction, square_in_union): the fifth loss of the reference's configuration (params_and_main.py:16), fastai
+ * losses.DiceLoss.  Logits z = B samples of HW pixels each (NHWC [B*HW, z_cs], slice z_co..z_co+C), targets int64 [B*HW]; per sample b
+ * and class c, with p = softmax(z) and t = onehot(y) (a target outside [0, C) is an all-zero row):
+ *   I = sum_hw p t,  U = sum_hw (p + t)  (square_in_union: sum_hw (p^2 + t)),  loss = sum_{b,c} 1 - (2 I + smooth) / (U + smooth),
+ * divided by mean_div when mean_div > 0 (reduction 'mean': B * C; tile-DDP: the global count of the terms), mean_div = 0: 'sum'.
+ * unet_dice_fwd writes loss[0] and coef [B][C][2] = (d loss / dI, d loss / dU) = (-2 / (U + s), (2 I + s) / (U + s)^2) / mean_div, which
+ * unet_dice_bwd reads: dz = gscale * d loss / d z (gscale multiplies: loss scaling).  workspace = unet_dice_workspace(B, HW, C) floats.
+ * C <= 64.  Deterministic: block partials per sample, summed in a fixed order in fp64. */
+size_t unet_dice_workspace(int B, long long HW, int C);   /* floats */
+int unet_dice_fwd(const float* z, int z_cs, int z_co, const int64_t* target, int B, long long HW, int C, float smooth, int square_in_union,
+                  long long mean_div, float* loss /*[1]*/, float* coef /*[B*C*2]*/, float* workspace, void* stream);
+int unet_dice_bwd(const float* z, int z_cs, int z_co, const int64_t* target, int B, long long HW, int C, int square_in_union,
+                  const float* coef, float gscale, float* dz, int dz_cs, int dz_co, void* stream);
 /* Regression mode (enable_regression, reference train.py:137-138,189-193; utils.py:145-147): n_out = 1, the loss is the mean over all
  * pixels of kind 0 = (z - t)^2 (MSELossFlat), 1 = |z - t| (L1LossFlat), 2 = SmoothL1(beta) (Smoothl1: beta 0.5).  z = channel z_co of
  * the NHWC output [P,z_cs], float targets [P]; workspace = unet_ce_workspace(P) floats.
@@ -437,6 +450,7 @@ int unet_nchw_to_nhwc_bf16(const float* x, unet_bf16* y, int y_cs, int y_co, int
 int unet_copy_slice_bf16(const unet_bf16* x, int x_cs, int x_co, unet_bf16* y, int y_cs, int y_co, long long P, int C, int accumulate, void* stream);
 int unet_ce_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C, const float* denom, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
 int unet_focal_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C, float gamma, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
+int unet_dice_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, int B, long long HW, int C, int square_in_union, const float* coef, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
 /* bf16 SelfAttention (round 3): the attention logits and the gradient of the attention weights stay fp32 (the products that make them write
  * fp32: unet_conv_desc.y_f32), the weights themselves and every other tensor are bf16 */
 int unet_pack_weights_strided_bf16(const unet_bf16* w, long long so, long long sr, unet_bf16* wp, int O, int R, void* stream);

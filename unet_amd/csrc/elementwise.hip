@@ -1112,6 +1112,134 @@ __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict_
     }
 }
 
+// DiceLoss(axis=1, smooth, reduction, square_in_union): fastai losses.DiceLoss, the fifth loss of the reference's configuration
+// (params_and_main.py:16).  Per sample b and class c over the sample's HW pixels, p = softmax(z), t = onehot(y) (a target outside [0, C):
+// an all-zero row):  I = sum p t,  U = sum (p + t)  [sum (p^2 + t) with square_in_union],  term = 1 - (2 I + s) / (U + s),
+// loss = sum_{b,c} term, divided by mean_div when mean_div > 0 ('mean': B * C, or the global count of the terms under tile-DDP).
+// A block never straddles two samples (grid = B x bps): block partials [B][bps][I(C), U(C)], then one wavefront sums them in a fixed
+// order in fp64 and writes, per (b, c), the coefficients of d loss / d p_c = a t_c + bc u'_c (u' = 1, or 2 p_c with square_in_union):
+//     a = -2 / (U + s) / mean_div,   bc = (2 I + s) / (U + s)^2 / mean_div.
+// The backward pass recomputes the softmax: dz_c = gscale * p_c (g_c - sum_k p_k g_k), g = a t + bc u'.  No atomics: bit-reproducible.
+// CB is a compile-time bound on C (C <= CB, loops fully unrolled): the per-class sums and logits live in registers, never in scratch.
+static int dice_bps(int B, long long HW) {
+    long long b = 1024 / B;                       // ~1024 blocks of 256 in all: enough waves to stream the logits at HBM rate
+    const long long most = (HW + 255) / 256;
+    if (b > most) b = most;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+template <int CB>
+__device__ __forceinline__ float dice_softmax(const float* __restrict__ zp, int C, float (&v)[CB]) {
+    float m = zp[0];
+#pragma unroll
+    for (int c = 0; c < CB; ++c)
+        if (c < C) { v[c] = zp[c]; m = fmaxf(m, v[c]); }
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < CB; ++c)
+        if (c < C) { v[c] = expf(v[c] - m); s += v[c]; }
+    return 1.f / s;                               // p_c = v[c] * (returned value)
+}
+
+template <int CB>
+__global__ __launch_bounds__(256) void dice_fwd_kernel(const float* __restrict__ z, int z_cs, int z_co, const int64_t* __restrict__ target,
+                                                       long long HW, int C, int bps, int square, float* __restrict__ part) {
+    const int b = blockIdx.x / bps, k = blockIdx.x - b * bps;
+    float I[CB], U[CB];
+#pragma unroll
+    for (int c = 0; c < CB; ++c) { I[c] = 0.f; U[c] = 0.f; }
+    const long long base = (long long)b * HW;
+    for (long long i = (long long)k * 256 + threadIdx.x; i < HW; i += (long long)bps * 256) {
+        const long long p = base + i;
+        const long long y = target[p];
+        float v[CB];
+        const float is = dice_softmax<CB>(z + (size_t)p * z_cs + z_co, C, v);
+#pragma unroll
+        for (int c = 0; c < CB; ++c) {
+            if (c >= C) continue;
+            const float pc = v[c] * is;
+            const bool hit = y == c;
+            I[c] += hit ? pc : 0.f;
+            U[c] += (square ? pc * pc : pc) + (hit ? 1.f : 0.f);
+        }
+    }
+    __shared__ float sI[4][CB], sU[4][CB];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < CB; ++c) {
+        if (c >= C) continue;
+        float a = I[c], u = U[c];
+        for (int o = 32; o > 0; o >>= 1) {
+            a += __shfl_down(a, o);
+            u += __shfl_down(u, o);
+        }
+        if (lane == 0) { sI[wv][c] = a; sU[wv][c] = u; }
+    }
+    __syncthreads();
+    float* row = part + (size_t)blockIdx.x * 2 * C;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        row[c] = sI[0][c] + sI[1][c] + sI[2][c] + sI[3][c];
+        row[C + c] = sU[0][c] + sU[1][c] + sU[2][c] + sU[3][c];
+    }
+}
+
+// one wavefront: lane j sums the bps partial rows of the (b, c) pairs j, j + 64, ... in fp64, in row order
+__global__ __launch_bounds__(64) void dice_finalize_kernel(const float* __restrict__ part, int B, int C, int bps, float smooth,
+                                                           long long mean_div, float* __restrict__ loss, float* __restrict__ coef) {
+    const double inv = mean_div > 0 ? 1.0 / (double)mean_div : 1.0, s = (double)smooth;
+    double acc = 0.0;
+    for (int j = threadIdx.x; j < B * C; j += 64) {
+        const int b = j / C, c = j - b * C;
+        const float* q = part + (size_t)b * bps * 2 * C + c;
+        double I = 0.0, U = 0.0;
+#pragma unroll 8
+        for (int r = 0; r < bps; ++r) {
+            I += (double)q[(size_t)r * 2 * C];
+            U += (double)q[(size_t)r * 2 * C + C];
+        }
+        const double num = 2.0 * I + s, den = U + s;
+        acc += 1.0 - num / den;
+        coef[2 * j] = (float)(-2.0 / den * inv);
+        coef[2 * j + 1] = (float)(num / (den * den) * inv);
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
+    if (threadIdx.x == 0) *loss = (float)(acc * inv);
+}
+
+template <int CB, typename T>
+__global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__ z, int z_cs, int z_co, const int64_t* __restrict__ target,
+                                                       long long HW, int C, int bps, int square, const float* __restrict__ coef, float gscale,
+                                                       T* __restrict__ dz, int dz_cs, int dz_co) {
+    const int b = blockIdx.x / bps, k = blockIdx.x - b * bps;
+    __shared__ float sa[CB], sb[CB];
+    for (int c = threadIdx.x; c < C; c += 256) {
+        sa[c] = gscale * coef[2 * ((size_t)b * C + c)];
+        sb[c] = gscale * coef[2 * ((size_t)b * C + c) + 1];
+    }
+    __syncthreads();
+    const long long base = (long long)b * HW;
+    for (long long i = (long long)k * 256 + threadIdx.x; i < HW; i += (long long)bps * 256) {
+        const long long p = base + i;
+        const long long y = target[p];
+        float v[CB];
+        const float is = dice_softmax<CB>(z + (size_t)p * z_cs + z_co, C, v);
+        float dot = 0.f;
+#pragma unroll
+        for (int c = 0; c < CB; ++c) {
+            if (c >= C) continue;
+            v[c] *= is;
+            dot += v[c] * ((y == c ? sa[c] : 0.f) + sb[c] * (square ? 2.f * v[c] : 1.f));
+        }
+        T* dp = dz + (size_t)p * dz_cs + dz_co;
+#pragma unroll
+        for (int c = 0; c < CB; ++c) {
+            if (c >= C) continue;
+            st1(dp + c, v[c] * ((y == c ? sa[c] : 0.f) + sb[c] * (square ? 2.f * v[c] : 1.f) - dot));
+        }
+    }
+}
+
 // Regression losses of the enable_regression branch (reference train.py:189-193: MSELossFlat(axis=1); utils.py:145-147:
 // Smoothl1 = SmoothL1Loss(beta=0.5); fastai L1LossFlat): prediction = channel 0 of the [P,1] output slice, float targets,
 // 'mean' reduction over all P pixels.  kind 0: d^2   1: |d|   2: |d| < beta ? d^2 / (2 beta) : |d| - beta / 2
@@ -1766,6 +1894,46 @@ extern "C" int unet_focal_bwd(const float* z, int z_cs, int z_co, const int64_t*
                               float gscale, float* dz, int dz_cs, int dz_co, void* stream) { return focal_bwd_impl<float>(z, z_cs, z_co, target, weight, P, C, gamma, gscale, dz, dz_cs, dz_co, stream); }
 extern "C" int unet_focal_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C, float gamma,
                               float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream) { return focal_bwd_impl<unet_bf16>(z, z_cs, z_co, target, weight, P, C, gamma, gscale, dz, dz_cs, dz_co, stream); }
+
+extern "C" size_t unet_dice_workspace(int B, long long HW, int C) {
+    if (B < 1 || HW < 1 || C < 1) return 0;
+    return (size_t)B * dice_bps(B, HW) * 2 * C;
+}
+
+extern "C" int unet_dice_fwd(const float* z, int z_cs, int z_co, const int64_t* target, int B, long long HW, int C, float smooth,
+                             int square_in_union, long long mean_div, float* loss, float* coef, float* workspace, void* stream) {
+    UNET_CHECK_ARG(z && target && loss && coef && workspace && B > 0 && HW > 0 && C > 0 && C <= CE_MAXC && mean_div >= 0, "dice_fwd: bad args");
+    UNET_CHECK_ARG(z_co >= 0 && z_co + C <= z_cs, "dice_fwd: bad slice");
+    const int bps = dice_bps(B, HW), sq = square_in_union ? 1 : 0;
+    const dim3 grid((unsigned)B * bps);
+    if (C <= 8) hipLaunchKernelGGL(dice_fwd_kernel<8>, grid, dim3(256), 0, ST, z, z_cs, z_co, target, HW, C, bps, sq, workspace);
+    else if (C <= 16) hipLaunchKernelGGL(dice_fwd_kernel<16>, grid, dim3(256), 0, ST, z, z_cs, z_co, target, HW, C, bps, sq, workspace);
+    else if (C <= 32) hipLaunchKernelGGL(dice_fwd_kernel<32>, grid, dim3(256), 0, ST, z, z_cs, z_co, target, HW, C, bps, sq, workspace);
+    else hipLaunchKernelGGL(dice_fwd_kernel<64>, grid, dim3(256), 0, ST, z, z_cs, z_co, target, HW, C, bps, sq, workspace);
+    UNET_CHECK_LAUNCH();
+    hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, ST, workspace, B, C, bps, smooth, mean_div, loss, coef);
+    UNET_CHECK_LAUNCH();
+    return UNET_OK;
+}
+
+template <typename T>
+static int dice_bwd_impl(const float* z, int z_cs, int z_co, const int64_t* target, int B, long long HW, int C, int square_in_union,
+                         const float* coef, float gscale, T* dz, int dz_cs, int dz_co, void* stream) {
+    UNET_CHECK_ARG(z && target && coef && dz && B > 0 && HW > 0 && C > 0 && C <= CE_MAXC, "dice_bwd: bad args");
+    UNET_CHECK_ARG(z_co >= 0 && z_co + C <= z_cs && dz_co >= 0 && dz_co + C <= dz_cs, "dice_bwd: bad slice");
+    const int bps = dice_bps(B, HW), sq = square_in_union ? 1 : 0;
+    const dim3 grid((unsigned)B * bps);
+    if (C <= 8) hipLaunchKernelGGL((dice_bwd_kernel<8, T>), grid, dim3(256), 0, ST, z, z_cs, z_co, target, HW, C, bps, sq, coef, gscale, dz, dz_cs, dz_co);
+    else if (C <= 16) hipLaunchKernelGGL((dice_bwd_kernel<16, T>), grid, dim3(256), 0, ST, z, z_cs, z_co, target, HW, C, bps, sq, coef, gscale, dz, dz_cs, dz_co);
+    else if (C <= 32) hipLaunchKernelGGL((dice_bwd_kernel<32, T>), grid, dim3(256), 0, ST, z, z_cs, z_co, target, HW, C, bps, sq, coef, gscale, dz, dz_cs, dz_co);
+    else hipLaunchKernelGGL((dice_bwd_kernel<64, T>), grid, dim3(256), 0, ST, z, z_cs, z_co, target, HW, C, bps, sq, coef, gscale, dz, dz_cs, dz_co);
+    UNET_CHECK_LAUNCH();
+    return UNET_OK;
+}
+extern "C" int unet_dice_bwd(const float* z, int z_cs, int z_co, const int64_t* target, int B, long long HW, int C, int square_in_union,
+                             const float* coef, float gscale, float* dz, int dz_cs, int dz_co, void* stream) { return dice_bwd_impl<float>(z, z_cs, z_co, target, B, HW, C, square_in_union, coef, gscale, dz, dz_cs, dz_co, stream); }
+extern "C" int unet_dice_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, int B, long long HW, int C, int square_in_union,
+                             const float* coef, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream) { return dice_bwd_impl<unet_bf16>(z, z_cs, z_co, target, B, HW, C, square_in_union, coef, gscale, dz, dz_cs, dz_co, stream); }
 
 extern "C" int unet_regloss_fwd(const float* z, int z_cs, int z_co, const float* target, long long P, int kind, float beta, float* loss,
                                 float* workspace, void* stream) {

@@ -8,7 +8,7 @@ train_bn, moms`` (``train.py:148-154``); ``unfreeze`` (``:246``); ``fit_one_cycl
 ``predict(item)`` -> 3-tuple whose [2] is per-class probabilities [C,H,W] (``predict.py:193-203``);
 ``get_preds``; ``summary``; callbacks ``SaveModelCallback(monitor, comp, fname)`` and ``CSVLogger`` (``train.py:209``);
 ``CrossEntropyLossFlat(axis=1, weight)`` with assignable ``.func.weight`` (``train.py:195,211``), ``FocalLossFlat(gamma, axis=1)``
-(``params_and_main.py:87-89``); ``DiceMulti``.
+(``params_and_main.py:87-89``), ``DiceLoss(axis=1, smooth, reduction, square_in_union)``; ``DiceMulti``.
 """
 from __future__ import annotations
 
@@ -96,6 +96,41 @@ class FocalLossFlat(CrossEntropyLossFlat):
         """Generic path (torch autograd)."""
         ce = torch.nn.functional.cross_entropy(logits, targ.long(), weight=self._w(logits.device), reduction="none")
         return ((1 - torch.exp(-ce)) ** self.gamma * ce).mean()
+
+
+class DiceLoss:
+    """fastai ``DiceLoss(axis=1, smooth=1e-6, reduction="sum", square_in_union=False)``, the fifth loss the reference's configuration imports
+    (params_and_main.py:16).  Per sample and class, with ``p = softmax(pred, dim=1)`` and ``t`` the one-hot target (a target outside [0, C) is
+    an all-zero row): ``1 - (2 sum(p t) + smooth) / (sum(p + t) + smooth)`` (``sum(p^2 + t)`` with square_in_union), summed or averaged
+    over the batch and the classes.  The signature and the defaults are the ones fastai documents for DiceLoss; fastai 2.5.1's source was not
+    available to check them against.  Fused on the device (unet_dice_fwd / unet_dice_bwd).  Class weights are NOT used: train.py:211 assigns
+    ``loss_func.func.weight`` for every loss (quirk Q5), so ``.func`` is a stand-in that keeps the assignment working.  At most 64 classes."""
+
+    def __init__(self, axis: int = 1, smooth: float = 1e-6, reduction: str = "sum", square_in_union: bool = False):
+        assert axis == 1
+        if reduction not in ("sum", "mean"):
+            raise ValueError(f"DiceLoss reduction must be 'sum' or 'mean', not {reduction!r}")
+        self.axis, self.smooth, self.reduction, self.square_in_union = axis, float(smooth), reduction, bool(square_in_union)
+        self.func = _Func(None)
+
+    def __call__(self, pred: torch.Tensor, targ: torch.Tensor) -> torch.Tensor:
+        """Generic path (torch autograd)."""
+        C = pred.shape[self.axis]
+        targ = targ.long()
+        t = torch.nn.functional.one_hot(targ.clamp(0, C - 1), C).movedim(-1, 1).to(pred.dtype)
+        t = t * ((targ >= 0) & (targ < C)).unsqueeze(1).to(pred.dtype)
+        p = self.activation(pred)
+        dims = list(range(2, pred.dim()))
+        inter = (p * t).sum(dims)
+        union = (p * p + t).sum(dims) if self.square_in_union else (p + t).sum(dims)
+        loss = 1 - (2.0 * inter + self.smooth) / (union + self.smooth)
+        return loss.mean() if self.reduction == "mean" else loss.sum()
+
+    def activation(self, x):
+        return torch.softmax(x, dim=self.axis)
+
+    def decodes(self, x):
+        return x.argmax(dim=self.axis)
 
 
 class _RegLoss:
@@ -682,6 +717,10 @@ class Learner:
         return self.loss_func.gamma if isinstance(self.loss_func, FocalLossFlat) else None
 
     @property
+    def _dice(self) -> Optional[DiceLoss]:
+        return self.loss_func if isinstance(self.loss_func, DiceLoss) else None
+
+    @property
     def regression(self) -> bool:
         return isinstance(self.loss_func, _RegLoss)
 
@@ -712,14 +751,18 @@ class Learner:
         """batch_cb(it, loss_tensor, lr) -> True stops the fit after that batch (lr_find)."""
         model, opt = self.model, self.opt
         self._sync_replicas()
-        fused = isinstance(self.loss_func, (CrossEntropyLossFlat, _RegLoss))
+        fused = isinstance(self.loss_func, (CrossEntropyLossFlat, _RegLoss, DiceLoss))
         if self.world > 1 and not fused:
-            raise RuntimeError("tile-DDP needs one of the fused losses (CrossEntropyLossFlat / MSELossFlat / L1LossFlat / Smoothl1)")
+            raise RuntimeError("tile-DDP needs one of the fused losses (CrossEntropyLossFlat / FocalLossFlat / DiceLoss / MSELossFlat / L1LossFlat / "
+                               "Smoothl1)")
+        if self._dice is not None and model.n_out > ops.CE_MAXC:
+            raise ValueError(f"DiceLoss supports at most {ops.CE_MAXC} classes, the model has {model.n_out}")
         step = TrainStep(model, opt, self._weights(), self.world) if fused else None
         if fused and self.regression:
             step.reg_kind, step.reg_beta = self.loss_func.kind, self.loss_func.beta
         if fused:
             step.focal_gamma = self._focal_gamma
+            step.dice = self._dice
         n_iter = len(self.dls.train)
         total = max(1, n_epoch * n_iter)
         for cb in self.cbs:
@@ -787,7 +830,13 @@ class Learner:
                 continue
             yb = yb.to(model._device, torch.int64).contiguous()
             loss, denom = ctx.vec(self, "vloss", 1), ctx.vec(self, "vden", 1)
-            if self._focal_gamma is not None:          # a plain mean over the pixels: numerator = loss * P, denominator = P
+            if self._dice is not None:                 # fastai AvgLoss: the batch losses weighted by the batch size
+                d = self._dice
+                ops.dice_fwd(z, yb, d.smooth, d.square_in_union, z.N * z.C if d.reduction == "mean" else 0, loss,
+                             ctx.vec(self, "vcoef", 2 * z.N * z.C), ctx.workspace(ops.dice_workspace(z.N, z.H * z.W, z.C)))
+                acc[0] += loss[0].double() * z.N
+                acc[1] += z.N
+            elif self._focal_gamma is not None:          # a plain mean over the pixels: numerator = loss * P, denominator = P
                 ops.focal_fwd(z, yb, w, self._focal_gamma, loss, ctx.workspace(ops.ce_workspace(z.P)))
                 acc[0] += loss[0].double() * z.P
                 acc[1] += z.P
@@ -964,6 +1013,8 @@ class Learner:
                 "class_weights": None if w is None else [float(v) for v in torch.as_tensor(w).cpu()],
                 "regression": self.loss_func.kind if self.regression else None,
                 "focal_gamma": self._focal_gamma,
+                **({"dice": {"smooth": self._dice.smooth, "reduction": self._dice.reduction, "square_in_union": self._dice.square_in_union}}
+                   if self._dice is not None else {}),
                 "self_attention": bool(getattr(m, "self_attention", False)), "act_dtype": getattr(m, "act_dtype", "f32")}
         p = Path(fname)
         p = p if p.is_absolute() else self.path / p
@@ -1000,10 +1051,19 @@ def load_learner(fname, device="cuda", act_dtype: Optional[str] = None) -> Learn
     model.load_state_dict(d["model"], strict=True)
     empty = TileDataset([], None, meta.get("dtype", "int8"))
     dls = DataLoaders(empty, None, 1, device=device, vocab=meta.get("vocab"))
-    w = meta.get("class_weights")
+    loss = _loss_from_meta(meta)
     if meta.get("regression"):
-        loss = {"mse": MSELossFlat, "l1": L1LossFlat, "smoothl1": Smoothl1}[meta["regression"]](axis=1)
         return Learner_adjust(dls, model, loss_func=loss, metrics=[Rmse(), R2Score()])
-    wt = None if w is None else torch.tensor(w)
-    loss = CrossEntropyLossFlat(axis=1, weight=wt) if meta.get("focal_gamma") is None else FocalLossFlat(gamma=meta["focal_gamma"], axis=1, weight=wt)
     return Learner(dls, model, loss_func=loss, metrics=[DiceMulti()])
+
+
+def _loss_from_meta(meta: dict):
+    """the loss object an exported file describes (Learner.export); files without a "dice" key load as they always have"""
+    if meta.get("regression"):
+        return {"mse": MSELossFlat, "l1": L1LossFlat, "smoothl1": Smoothl1}[meta["regression"]](axis=1)
+    if meta.get("dice") is not None:
+        d = meta["dice"]
+        return DiceLoss(axis=1, smooth=d["smooth"], reduction=d["reduction"], square_in_union=d["square_in_union"])
+    w = meta.get("class_weights")
+    wt = None if w is None else torch.tensor(w)
+    return CrossEntropyLossFlat(axis=1, weight=wt) if meta.get("focal_gamma") is None else FocalLossFlat(gamma=meta["focal_gamma"], axis=1, weight=wt)

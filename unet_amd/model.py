@@ -461,7 +461,7 @@ class HipDynamicUnet(nn.Module):
 
     def forward_loss_backward(self, x: torch.Tensor, y: torch.Tensor, weight: Optional[torch.Tensor] = None,
                               grad_scale: float = 1.0, reg_kind: Optional[str] = None, reg_beta: float = 0.5,
-                              world: int = 1, focal_gamma: Optional[float] = None) -> torch.Tensor:
+                              world: int = 1, focal_gamma: Optional[float] = None, dice=None) -> torch.Tensor:
         """One fused training pass: logits -> loss -> backward into the flat gradient buffer.  Returns the loss as a 1-element
         device tensor (no host sync).  grad_scale multiplies the gradient.
         world > 1 (tile-DDP): the weighted cross-entropy is sum_r num_r / sum_r den_r over the ranks (den_r = sum of w[y] on
@@ -472,13 +472,44 @@ class HipDynamicUnet(nn.Module):
         Classification (default): weighted per-pixel cross-entropy, CrossEntropyLossFlat(axis=1, weight) (train.py:195,211).
         focal_gamma: FocalLossFlat(gamma, axis=1) instead (params_and_main.py:87-89): a plain mean over equally many pixels per rank, like the
         regression losses -- loss averaged over the ranks, gradient pre-scaled by 1 / world.
+        dice: DiceLoss instead (params_and_main.py:16) -- any object with .smooth, .reduction ("sum" | "mean") and .square_in_union; class
+        weights are not used.  Every (sample, class) term depends on one sample only: 'sum' needs no 1 / world pre-scale and the loss is
+        SUM all-reduced; 'mean' divides by the global count of the terms (all-reduced with the loss, applied to the gradient coefficients).
         Regression (reg_kind = "mse" | "l1" | "smoothl1", n_out = 1, float targets [B,H,W]): train.py:189-193."""
+        if dice is not None:
+            if reg_kind is not None:
+                raise ValueError("DiceLoss is a classification loss: it cannot be combined with a regression loss")
+            if self.n_out > ops.CE_MAXC:
+                raise ValueError(f"DiceLoss supports at most {ops.CE_MAXC} classes, the model has {self.n_out}")
+            if dice.reduction not in ("sum", "mean"):
+                raise ValueError(f"DiceLoss reduction must be 'sum' or 'mean', not {dice.reduction!r}")
         x = x.to(self._device, torch.float32)
         z = self._hip_forward(x, True)
         ctx = self.ctx
         P = z.P
         dz = ctx.act(self, "dlogits", z.N, z.H, z.W, z.C, zero=True)
-        if reg_kind is None and focal_gamma is not None:
+        if dice is not None:
+            y = y.to(self._device, torch.int64).contiguous()
+            loss, coef = ctx.vec(self, "loss", 1), ctx.vec(self, "dice_coef", 2 * z.N * z.C)
+            mean = dice.reduction == "mean"
+            ws = ctx.workspace(ops.dice_workspace(z.N, z.H * z.W, z.C))
+            if world > 1:
+                import torch.distributed as dist
+                # this rank's sum of the terms and, for 'mean', its count of them: one all-reduce, then the global mean
+                ops.dice_fwd(z, y, dice.smooth, dice.square_in_union, 0, loss, coef, ws)
+                if mean:
+                    lc = ctx.vec(self, "dice_lc", 2)
+                    lc[0:1].copy_(loss)
+                    lc[1].fill_(float(z.N * z.C))
+                    dist.all_reduce(lc)
+                    torch.div(lc[0:1], lc[1:2], out=loss)
+                    coef.div_(lc[1:2])
+                else:
+                    dist.all_reduce(loss)
+            else:
+                ops.dice_fwd(z, y, dice.smooth, dice.square_in_union, z.N * z.C if mean else 0, loss, coef, ws)
+            ops.dice_bwd(z, y, dice.square_in_union, coef, grad_scale, dz)
+        elif reg_kind is None and focal_gamma is not None:
             y = y.to(self._device, torch.int64).contiguous()
             loss = ctx.vec(self, "loss", 1)
             ops.focal_fwd(z, y, weight, focal_gamma, loss, ctx.workspace(ops.ce_workspace(P)))

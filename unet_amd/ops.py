@@ -675,6 +675,9 @@ def dot(x: TS, y: TS, out: torch.Tensor, ws: torch.Tensor):
 
 # ------------------------------------------------------------------ loss
 
+CE_MAXC = 64        # most classes the classification-loss kernels take (elementwise.hip CE_MAXC)
+
+
 def ce_workspace(P) -> int:
     return int(lib.unet_ce_workspace(P))
 
@@ -710,6 +713,29 @@ def focal_fwd(z: TS, target: torch.Tensor, weight, gamma: float, loss, ws):
 def focal_bwd(z: TS, target, weight, gamma: float, gscale: float, dz: TS):
     check(_fn("focal_bwd", dz)(z.ptr, z.cs, z.co, target.data_ptr(), _p(weight), z.P, z.C, float(gamma), gscale, dz.ptr, dz.cs, dz.co, _stream()),
           "focal_bwd")
+
+
+def dice_workspace(B: int, HW: int, C: int) -> int:
+    return int(lib.unet_dice_workspace(B, HW, C))
+
+
+def dice_fwd(z: TS, target: torch.Tensor, smooth: float, square_in_union: bool, mean_div: int, loss, coef, ws):
+    """fastai DiceLoss over the z.N samples of the slice: loss[0] = sum_{b,c} 1 - (2 I + smooth) / (U + smooth), divided by mean_div when
+    mean_div > 0 ('mean'); coef [N*C*2] receives d loss / dI and d loss / dU per (sample, class) for dice_bwd"""
+    _need_f32("dice_fwd", z)
+    if z.C > CE_MAXC:
+        raise ValueError(f"dice_fwd: at most {CE_MAXC} classes, got {z.C}")
+    HW = z.H * z.W
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == z.P
+    assert coef.dtype == torch.float32 and coef.numel() >= 2 * z.N * z.C and ws.numel() >= dice_workspace(z.N, HW, z.C)
+    check(lib.unet_dice_fwd(z.ptr, z.cs, z.co, target.data_ptr(), z.N, HW, z.C, float(smooth), int(bool(square_in_union)), int(mean_div),
+                            loss.data_ptr(), coef.data_ptr(), ws.data_ptr(), _stream()), "dice_fwd")
+
+
+def dice_bwd(z: TS, target, square_in_union: bool, coef, gscale: float, dz: TS):
+    assert dz.N == z.N and dz.H == z.H and dz.W == z.W and dz.C == z.C and coef.numel() >= 2 * z.N * z.C
+    check(_fn("dice_bwd", dz)(z.ptr, z.cs, z.co, target.data_ptr(), z.N, z.H * z.W, z.C, int(bool(square_in_union)), coef.data_ptr(),
+                              float(gscale), dz.ptr, dz.cs, dz.co, _stream()), "dice_bwd")
 
 
 REG_KINDS = {"mse": 0, "l1": 1, "smoothl1": 2}
