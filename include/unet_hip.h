@@ -428,6 +428,23 @@ int unet_mask_stage(const void* src, int rtype, int n, int H, int W, unsigned lo
  * [2][c] += #(clamp(targ, 0, C - 1) == c).  C <= 64. */
 int unet_dice_counts(const int64_t* pred, const int64_t* targ, long long P, int C, unsigned long long* counts, void* stream);
 
+/* ---------------------------------------------------- geometric augmentation --
+ * The rotate / transpose / shift-scale-rotate augmentations of unet_amd.augment (albumentations RandomRotate90, Transpose, Rotate,
+ * ShiftScaleRotate: cv2.warpAffine per image on the host in the reference's pipeline, params_and_main.py:105-115) on a device batch.
+ * Output pixel (x, y) of image j takes the source value at (m[0] x + m[1] y + m[2], m[3] x + m[4] y + m[5]), m = inv_maps_host + 6 j:
+ * the INVERSE affine map, n x 6 fp32 in host memory, read at call time and passed in the kernel arguments (n <= 64).  Out of place
+ * (src == dst is refused); the output has the input's size.  interp: 0 nearest (floor(s + 0.5)), 1 bilinear (fp32 weights, without cv2's
+ * 1/32-pixel quantisation).  border: cv2 codes 0 constant (fill), 1 replicate, 2 reflect, 4 reflect-101, for coordinates any distance
+ * outside the image.  Every tap is mapped into the image or replaced by fill; nothing is read or written outside src / dst.
+ * unet_warp_affine: src / dst [n, C, H, W] fp32.
+ * unet_warp_affine_mask: nearest always; src / dst [n, H, W] int64 (dst_f32 = 0, classification) or fp32 (dst_f32 = 1, regression).
+ * Both return -1 before any launch on a null pointer, n outside 1..64, a size outside 1..2^24, an unknown interp / border, or a
+ * non-finite map entry or fill. */
+int unet_warp_affine(const float* src, float* dst, int n, int C, int H, int W, const float* inv_maps_host, int interp, int border, float fill,
+                     void* stream);
+int unet_warp_affine_mask(const void* src, void* dst, int dst_f32, int n, int H, int W, const float* inv_maps_host, int border, double fill,
+                          void* stream);
+
 /* ---------------------------------------------------- bf16-storage twins --
  * The HBM-bound kernels of the step with bf16 activation / gradient tensors (per-channel vectors, statistics, indices, losses stay
  * as in the fp32 entry point of the same name; arithmetic is fp32 per element, one rounding to bf16 at the store).  Used by

@@ -67,6 +67,7 @@ n_transform_imgs = 1
 # None = the reference's default pipeline HorizontalFlip(p=0.5) + VerticalFlip(p=0.5); or, with `from unet_amd import augment as A`:
 # A.Compose([A.HorizontalFlip(p=0.5), A.VerticalFlip(p=0.5),
 #            A.RandomBrightnessContrast(brightness_limit=(-0.1, 0.1), contrast_limit=(-0.1, 0.1), p=0.5), A.CoarseDropout(p=0.5)])
+# Geometric: A.RandomRotate90(p=0.5), A.Transpose(p=0.5), A.Rotate(limit=90, p=0.5), A.ShiftScaleRotate(p=0.5) (square tiles for the first two)
 aug_pipe = None
 
 

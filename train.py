@@ -154,8 +154,9 @@ def train_func(data_path, existing_model, model_Path, description, BATCH_SIZE, v
     tfm = None
     if transforms:
         # aug_pipe: None = the reference's default pipeline HorizontalFlip + VerticalFlip (params_and_main.py:105-115); or a
-        # unet_amd.augment.Compose (HorizontalFlip / VerticalFlip / RandomBrightnessContrast / CoarseDropout with albumentations'
-        # semantics, applied on the device); a ready batch transform (FlipAugment / BatchAugment) is used as is
+        # unet_amd.augment.Compose (HorizontalFlip / VerticalFlip / RandomRotate90 / Transpose / Rotate / ShiftScaleRotate /
+        # RandomBrightnessContrast / CoarseDropout with albumentations' semantics, applied on the device); a ready batch transform
+        # (FlipAugment / BatchAugment) is used as is
         from unet_amd.augment import BatchAugment, Compose
         if isinstance(aug_pipe, (FlipAugment, BatchAugment)):
             tfm = aug_pipe

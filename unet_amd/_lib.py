@@ -180,6 +180,8 @@ _sig = {
     "unet_tiles_stage": (i, [vp, i, i, i, i, i, i, C.c_ulonglong, C.c_ulonglong, vp, vp]),
     "unet_mask_stage": (i, [vp, i, i, i, i, C.c_ulonglong, C.c_ulonglong, vp, i, vp]),
     "unet_dice_counts": (i, [vp, vp, ll, i, vp, vp]),
+    "unet_warp_affine": (i, [vp, vp, i, i, i, i, c_float_p, i, i, f, vp]),
+    "unet_warp_affine_mask": (i, [vp, vp, i, i, i, i, c_float_p, i, C.c_double, vp]),
 }
 # bf16-storage twins: same argument lists (every tensor is a void pointer on this side)
 for _n in ("bn_stats", "affine_act", "bn_bwd_reduce", "bn_bwd_apply", "maxpool3x3s2", "maxpool3x3s2_bwd", "avgpool2_ceil",

@@ -889,6 +889,45 @@ def dice_counts(pred: torch.Tensor, targ: torch.Tensor, n_cls: int, counts: torc
     check(lib.unet_dice_counts(pred.data_ptr(), targ.data_ptr(), pred.numel(), n_cls, counts.data_ptr(), _stream()), "dice_counts")
 
 
+# ------------------------------------------------------------------ geometric augmentation (csrc/warp.hip: unet_warp_affine[_mask])
+
+def _warp_args(what: str, src: torch.Tensor, dst: torch.Tensor, inv_maps, dims: int):
+    if not (src.is_cuda and dst.is_cuda):
+        raise RuntimeError(f"{what}: the warp runs on the device only (HIP, no CPU fallback); got {src.device} / {dst.device} tensors")
+    assert src.dim() == dims and src.is_contiguous() and dst.is_contiguous() and src.shape == dst.shape and src.dtype == dst.dtype, \
+        (what, src.shape, dst.shape, src.dtype, dst.dtype)
+    import numpy as np
+    maps = np.ascontiguousarray(inv_maps, dtype=np.float32).reshape(-1, 6)
+    assert maps.shape[0] == src.shape[0], (what, maps.shape, src.shape)
+    return maps
+
+
+def warp_affine(src: torch.Tensor, dst: torch.Tensor, inv_maps, interp: int, border: int, fill: float = 0.0):
+    """dst[j] = src[j] sampled at inv_maps[j] (2 x 3 per image, output -> source) with interp 0 nearest / 1 bilinear and a cv2 border
+    code; src / dst [n, C, H, W] fp32 on the device, out of place"""
+    maps = _warp_args("warp_affine", src, dst, inv_maps, 4)
+    assert src.dtype == torch.float32, src.dtype
+    n, Cc, H, W = src.shape
+    per = Cc * H * W
+    for at in range(0, n, 64):
+        m = min(64, n - at)
+        check(lib.unet_warp_affine(src.data_ptr() + at * per * 4, dst.data_ptr() + at * per * 4, m, Cc, H, W,
+                                   maps[at:at + m].ctypes.data_as(L.c_float_p), int(interp), int(border), float(fill), _stream()), "warp_affine")
+
+
+def warp_affine_mask(src: torch.Tensor, dst: torch.Tensor, inv_maps, border: int, fill: float = 0.0):
+    """the nearest-neighbour warp of masks [n, H, W] int64 (classification) or fp32 (regression targets), same maps as warp_affine"""
+    maps = _warp_args("warp_affine_mask", src, dst, inv_maps, 3)
+    assert src.dtype in (torch.int64, torch.float32), src.dtype
+    n, H, W = src.shape
+    es = src.element_size()
+    for at in range(0, n, 64):
+        m = min(64, n - at)
+        check(lib.unet_warp_affine_mask(src.data_ptr() + at * H * W * es, dst.data_ptr() + at * H * W * es, int(src.dtype == torch.float32),
+                                        m, H, W, maps[at:at + m].ctypes.data_as(L.c_float_p), int(border), float(fill), _stream()),
+              "warp_affine_mask")
+
+
 def mosaic_accumulate_windows(z: TS, table: torch.Tensor, first: int, n: int, origin, mosaic: torch.Tensor, count: torch.Tensor,
                               row_lo: int, row_hi: int, raw: bool = False):
     """softmax (or, raw=True, the values themselves) of the fp32 NHWC logits of windows [first, first + n) added into mosaic / count"""
