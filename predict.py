@@ -257,6 +257,36 @@ def _want(regression, all_classes, specific_class):
 
 # ----------------------------------------------------------------------------------------------- configs[4]: a whole raster
 
+def _check_windows(rows, th: int, tw: int, H: int, W: int, sources: int = 1):
+    """host check of a window table before it is uploaded: every row (y0, x0[, source]) must cut a th x tw window out of one of
+    `sources` H x W images -- the gather kernels are not told the raster's height and trust the table"""
+    a = np.asarray(rows, dtype=np.int64).reshape(len(rows), -1)
+    if not len(a):
+        return
+    src = a[:, 2] if a.shape[1] > 2 else np.zeros(len(a), dtype=np.int64)
+    bad = (a[:, 0] < 0) | (a[:, 1] < 0) | (a[:, 0] + th > H) | (a[:, 1] + tw > W) | (src < 0) | (src >= sources)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"window {i} {a[i].tolist()} of {th} x {tw} px does not lie inside the {sources} source(s) of {H} x {W} px")
+
+
+def _check_batch(first: int, n: int, n_pad: int, table_rows: int):
+    """a batch reads table rows [first, first + n_pad) (n real windows, the rest repeats): they must exist"""
+    if not (first >= 0 and 0 < n <= n_pad and first + n_pad <= table_rows):
+        raise ValueError(f"batch of table rows [{first}, {first + n_pad}) (n = {n}) outside a table of {table_rows} rows")
+
+
+def _raster_plan(wins: np.ndarray, size: int, H: int, W: int, batch_size: int):
+    """kept windows (y0, x0) in merge order -> (placements [n, 4] in mosaic coordinates, MH, MW, oy, ox, gather-table rows in raster
+    coordinates, padded at the end with batch_size repeats of the last window so that the last batch of any rank can be filled up)"""
+    _check_windows(wins, size, size, H, W)
+    oy, ox = int(wins[:, 0].min()), int(wins[:, 1].min())                          # extent of the tiles present (predict.py:259-270)
+    MH, MW = int(wins[:, 0].max()) + size - oy, int(wins[:, 1].max()) + size - ox
+    places = np.concatenate([wins - np.array([oy, ox]), np.full((len(wins), 2), size, dtype=np.int64)], axis=1)
+    rows = wins.tolist() + [wins[-1].tolist()] * batch_size
+    return places, MH, MW, oy, ox, rows
+
+
 def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_empty: float = 0.9, dtype: str = "int8", nodata=None,
                    regression: bool = False, all_classes: bool = False, specific_class: Optional[int] = None, large_file: bool = False,
                    batch_size: int = 16, out_path=None, class_zero: bool = False, timing: Optional[dict] = None,
@@ -302,20 +332,18 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
         ops.raster_nodata_zero(src, nodata)                                        # create_tiles_unet.py:344-352
     Cb, H, W = src.C, src.H, src.W
     wins = sliding_windows(H, W, size, overlap)                                    # create_tiles_unet.py:52-54
+    _check_windows(wins, size, size, H, W)
     table_all = ops.window_table(wins.tolist(), dev)
     nz = ops.window_nonzero(src, table_all, size, size).cpu().numpy()
     keep = keep_windows(nz, Cb, size, size, max_empty)                             # create_tiles_unet.py:379
     wins = wins[keep]
     if len(wins) == 0:
         raise ValueError("every window of the raster is emptier than max_empty: nothing to predict")
-    oy, ox = int(wins[:, 0].min()), int(wins[:, 1].min())                          # extent of the tiles present (predict.py:259-270)
-    MH, MW = int(wins[:, 0].max()) + size - oy, int(wins[:, 1].max()) + size - ox
-    places = np.concatenate([wins - np.array([oy, ox]), np.full((len(wins), 2), size, dtype=np.int64)], axis=1)
-    # gather table in raster coordinates, padded at the end so that the last batch can be filled up with repeats of the last window
-    rows = wins.tolist() + [wins[-1].tolist()] * batch_size
+    places, MH, MW, oy, ox, rows = _raster_plan(wins, size, H, W, batch_size)
     gtab = ops.window_table(rows, dev)
 
     def make_input(first, n, n_pad):
+        _check_batch(first, n, n_pad, len(rows))
         return ops.WindowBatch(src, gtab, first, n_pad, size, size)
 
     want = _want(regression, all_classes, specific_class)
@@ -491,7 +519,8 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
         plan = MergePlan(places, MH, MW, world)
         pf = _prefetcher(tiles_o, plan.batches(rank, batch_size), [(int(p_[2]), int(p_[3])) for p_ in places], dev)
         feed = iter(pf)
-        ztab = ops.window_table([[0, 0, j, 0] for j in range(batch_size)], dev)
+        zrows = [[0, 0, j, 0] for j in range(batch_size)]
+        ztab = ops.window_table(zrows, dev)
         held = []          # staging slot of the batch in flight: released once the NEXT batch is asked for (its gather has been issued by then)
 
         def make_input(first, n, n_pad):
@@ -500,6 +529,8 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
             f, nn, buf = next(feed)
             d = pf.upload(buf, dev)
             assert (f, nn) == (first, n) and d.shape[0] == n_pad, ((f, nn, d.shape[0]), (first, n, n_pad))
+            _check_batch(0, n, n_pad, len(zrows))
+            _check_windows(zrows[:n_pad], d.shape[2], d.shape[3], d.shape[2], d.shape[3], sources=d.shape[0])
             if hasattr(pf, "done"):
                 held.append(buf)
             return ops.WindowBatch(ops.WindowSource(d, div255_twice=div2), ztab, 0, n_pad, d.shape[2], d.shape[3])
@@ -534,9 +565,12 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
         i += n
     mtiles = [tiles[i] for i in mine]
     pf = _prefetcher(mtiles, batches, sizes, dev)
-    ztab = ops.window_table([[0, 0, j, 0] for j in range(batch_size)], dev)
+    zrows = [[0, 0, j, 0] for j in range(batch_size)]
+    ztab = ops.window_table(zrows, dev)
     for first, n, buf in pf:
         d = pf.upload(buf, dev)
+        _check_batch(0, n, d.shape[0], len(zrows))
+        _check_windows(zrows[:d.shape[0]], d.shape[2], d.shape[3], d.shape[2], d.shape[3], sources=d.shape[0])
         wb = ops.WindowBatch(ops.WindowSource(d, div255_twice=div2), ztab, 0, d.shape[0], d.shape[2], d.shape[3])
         with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
             z = model.forward_windows(wb)
