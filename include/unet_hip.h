@@ -411,6 +411,24 @@ int unet_mosaic_accumulate_windows(const float* z, int z_cs, int z_co, int C, in
 int unet_mosaic_finalize_rows(float* mosaic, const int32_t* count, int C, int MH, int MW, int row0, int nrows, uint8_t* argmax,
                               const float* fill_host, void* stream);
 
+/* Test-time augmentation (TTA).  A D4 code g names one of the 8 symmetries of the square, by its action on the last two axes
+ * [..., H, W] of a tensor: 0 x, 1 flip(x, [-1]), 2 flip(x, [-2]), 3 flip(x, [-2, -1]), 4 x^T, 5 rot90(x, 1, (-2, -1)),
+ * 6 rot90(x, -1, (-2, -1)), 7 flip(x^T, [-2, -1]); the inverse of 5 is 6 and vice versa, every other code is its own inverse.  Codes
+ * 4..7 need square windows / images (else UNET_E_BADARG).  Every map is an exact index permutation. */
+/* unet_window_gather with window j written as g(window j) (same casts and divisions bit for bit) */
+int unet_window_gather_oriented(const void* src, int rtype, int bands, long long src_stride, long long band_stride, int row_stride,
+                                const int32_t* windows, int n, int th, int tw, int div255_twice, void* x, int x_cs, int x_co, int dtype,
+                                int orient, void* stream);
+/* unet_nchw_to_nhwc (dtype UNET_F32 | UNET_BF16 storage of y) with image n written as g(x[n]) */
+int unet_nchw_to_nhwc_oriented(const float* x, void* y, int y_cs, int y_co, int N, int C, int H, int W, int dtype, int orient, void* stream);
+/* acc [n, th, tw, acc_cs] (fp32, channels [0, C)) = (first ? 0 : acc) + g^-1(softmax(z)) (mode 0, the arithmetic of unet_softmax_argmax)
+ * or + g^-1(z) (mode 1, regression), z the fp32 NHWC logits [n, th, tw, z_cs] of windows produced under code g = orient.  One thread per
+ * acc pixel: the codes of a set add in launch order (no atomics).  finalize_k > 0 (the last code of a set of k): acc /= k (one rounded
+ * division) in place, and probs (NCHW [n, C, th, tw], may be NULL) and argmax (int64 [n, th, tw], first maximum, may be NULL) are
+ * written; with finalize_k == 0 both must be NULL. */
+int unet_tta_accumulate(const float* z, int z_cs, int z_co, int n, int C, int th, int tw, int orient, int mode, int first, float* acc,
+                        int acc_cs, int finalize_k, float* probs, int64_t* argmax, void* stream);
+
 /* ------------------------------------------------------- training feed --
  * What learn.fit_one_cycle's loader does per batch on the host in the reference (train.py:345 -> data.py:18-28 open_npy: tile -> int32 ->
  * float; utils.py:239-295 SegmentationAlbumentationsTransform: / 255 for int8 data, / 255 twice for int16 data, flips on the first

@@ -69,11 +69,14 @@ n_transform_imgs = 1
 #            A.RandomBrightnessContrast(brightness_limit=(-0.1, 0.1), contrast_limit=(-0.1, 0.1), p=0.5), A.CoarseDropout(p=0.5)])
 # Geometric: A.RandomRotate90(p=0.5), A.Transpose(p=0.5), A.Rotate(limit=90, p=0.5), A.ShiftScaleRotate(p=0.5) (square tiles for the first two)
 aug_pipe = None
+# test-time augmentation of Predict: None | "flips" (4 passes, any tile shape) | "d4" (8 passes, square tiles) | a tuple of D4 codes
+# (unet_amd/tta.py); every tile's probabilities become the mean over the flipped / rotated passes, mapped back
+TTA = None
 
 
 def main():
     global large_file, specific_class, all_classes, transforms, VALID_SCENES, self_attention, monitor, loss_func, LR_FINDER
-    global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty
+    global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA
     t0 = time.time()
     if enable_extra_parameters:          # params_and_main.py:129-145
         import warnings
@@ -83,6 +86,7 @@ def main():
         ENCODER_FACTOR, LR_FINDER, VALID_SCENES, loss_func, monitor = 10, None, ["vali"], None, None
         all_classes, specific_class, enable_regression, large_file, max_empty = False, None, False, False, 0.9
         ARCHITECTURE, self_attention = xresnet34, False
+        TTA = None
     if Create_tiles:
         from create_tiles_unet import split_raster
         split_raster(path_to_raster=image_path, path_to_mask=mask_path, base_dir=base_dir, patch_size=patch_size,
@@ -95,7 +99,7 @@ def main():
     if Predict:
         from predict import save_predictions
         save_predictions(predict_model, predict_path, regression, merge, all_classes, specific_class, large_file, AOI, year,
-                         validation_vision, class_zero)
+                         validation_vision, class_zero, tta=TTA)
     print(f"Operation completed in {(time.time() - t0) / 60:.2f} minutes.")
 
 

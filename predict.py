@@ -16,6 +16,12 @@ Differences that keep the results but not the schedule:
   travel as per-window slabs to the neighbouring rank, and only the requested band(s) -- the uint8 argmax by default -- reach rank 0 and the host.
 ``regression`` predicts the raw single-band output (merged mosaic = mean of the overlapping tiles, nodata -9999 where no tile was
 placed).  The confusion-matrix plots (``predict.py:56-143``) are reporting and out of scope.
+
+Beyond the reference: ``tta=`` (None | "flips" | "d4" | a tuple of D4 codes, ``unet_amd/tta.py``) adds test-time augmentation to both entry
+points, merged and per tile.  Every batch runs k forwards of the same geometry on oriented windows (``unet_window_gather_oriented``); the
+outputs are mapped back and averaged per window on the device in code order (``unet_tta_accumulate``), and that mean takes the place of the
+window's softmax probabilities in the merge, the slabs, the int8 ``large_file`` merge and the per-tile outputs.  The hit counter still counts
+windows.
 """
 from __future__ import annotations
 
@@ -35,6 +41,7 @@ from unet_amd import ops
 from unet_amd.learner import load_learner, open_tile
 from unet_amd.mosaic import MergePlan, keep_windows, merge_order, sliding_windows
 from unet_amd.tiffio import read_tiff, tiff_info, write_tiff
+from unet_amd.tta import parse as tta_codes
 
 
 def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_zero=False):
@@ -130,18 +137,23 @@ class _Merge:
         self.mosaic[:, y + r0:y + r1, x:x + q.shape[2]] += q[:, r0:r1]
         self.count[:, y + r0:y + r1, x:x + q.shape[2]] += 1
 
-    def add_batch(self, first: int, n: int, z: ops.TS):
-        """logits z [>= n, h, w, C] of placements [first, first + n)"""
+    def add_batch(self, first: int, n: int, z: ops.TS, values: bool = False):
+        """logits z [>= n, h, w, C] of placements [first, first + n); values=True: z already holds the window's probabilities (or
+        regression outputs) -- the finalised TTA accumulator -- and is added as it is"""
         rows = self.hi - self.lo
+        raw = self.raw or values
         if rows > 0:
             if self.int8:
                 probs = torch.empty((n, self.C, z.H, z.W), dtype=torch.float32, device=self.dev)
-                ops.softmax_argmax(ops.TS(z.buf[:n], z.co, z.C), probs, None)
+                if values:
+                    ops.nhwc_to_nchw(ops.TS(z.buf[:n], z.co, z.C), probs)
+                else:
+                    ops.softmax_argmax(ops.TS(z.buf[:n], z.co, z.C), probs, None)
                 for j in range(n):
                     y0, x0 = self.plan.places[first + j, :2]
                     self._add_int8(probs[j], int(y0) - self.lo, int(x0))
             else:
-                ops.mosaic_accumulate_windows(z, self.acc_table, first, n, (self.lo, 0), self.mosaic, self.count, 0, rows, raw=self.raw)
+                ops.mosaic_accumulate_windows(z, self.acc_table, first, n, (self.lo, 0), self.mosaic, self.count, 0, rows, raw=raw)
         for j in range(n):          # rows that belong to the strip above: per-window slabs for rank - 1
             ent = self._slab_off.get(first + j)
             if ent is None:
@@ -150,7 +162,7 @@ class _Merge:
             w = int(self.plan.places[first + j, 3])
             out = self.sendbuf[off:off + self.C * r * w].view(1, self.C, r, w)
             zs = ops.TS(z.buf[j:j + 1, :r], z.co, z.C)
-            if self.raw:
+            if raw:
                 ops.nhwc_to_nchw(zs, out)
             else:
                 ops.softmax_argmax(zs, out, None)
@@ -218,18 +230,46 @@ class _Merge:
         return full.cpu().numpy()
 
 
-def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch, make_input: Callable, want, timing: Optional[dict] = None):
+class _TTAAccumulator:
+    """the dense fp32 NHWC accumulator [n_pad, h, w, C] of one call (re-made only when a batch of another tile size arrives)"""
+
+    def __init__(self, model, codes: Tuple[int, ...], raw: bool):
+        self.model, self.codes, self.raw = model, codes, raw
+        self.buf: Optional[torch.Tensor] = None
+
+    def run(self, wb: ops.WindowBatch, n: int, probs: Optional[torch.Tensor] = None, amax: Optional[torch.Tensor] = None) -> ops.TS:
+        """k forwards of the batch (ONE geometry: n_pad windows), the n real windows' outputs mapped back and averaged on the device;
+        the last launch also writes probs (NCHW) / amax (int64) when given"""
+        C = self.model.n_out
+        shape = (wb.n, wb.th, wb.tw, ops.rup4(C))
+        if self.buf is None or tuple(self.buf.shape) != shape:
+            self.buf = torch.empty(shape, dtype=torch.float32, device=self.model._device)
+        k = len(self.codes)
+        for i, g in enumerate(self.codes):
+            z = self.model.forward_windows_oriented(wb, g)
+            last = i == k - 1
+            ops.tta_accumulate(z, n, g, self.raw, i == 0, self.buf, k if last else 0, probs if last else None, amax if last else None)
+        return ops.TS(self.buf, 0, C)
+
+
+def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch, make_input: Callable, want, timing: Optional[dict] = None,
+               tta: Optional[Tuple[int, ...]] = None):
     """make_input(first, n, n_pad) -> ops.WindowBatch of placements [first, first + n) padded to n_pad windows (so that every
-    forward runs on ONE batch geometry and no second set of activation buffers is allocated)"""
+    forward runs on ONE batch geometry and no second set of activation buffers is allocated).  tta: parsed codes -- every batch runs
+    len(tta) forwards of that same geometry and the averaged probabilities take the place of the softmax in the merge"""
     mg = _Merge(model, places, MH, MW, regression, int8_merge, rank, world, batch)
+    acc = None if tta is None else _TTAAccumulator(model, tta, bool(regression))
     t0 = time.perf_counter()
     done = 0
     batches = mg.plan.batches(rank, batch)
     n_pad = max((n for _, n in batches), default=0)
     for first, n in batches:
         wb = make_input(first, n, n_pad)
-        z = model.forward_windows(wb)
-        mg.add_batch(first, n, z)
+        if acc is None:
+            z = model.forward_windows(wb)
+            mg.add_batch(first, n, z)
+        else:
+            mg.add_batch(first, n, acc.run(wb, n), values=True)
         done += n
     mg.exchange()
     if timing is not None and not int8_merge and mg.hi > mg.lo:      # coverage of this rank's strip (before the division consumes nothing of it)
@@ -290,7 +330,7 @@ def _raster_plan(wins: np.ndarray, size: int, H: int, W: int, batch_size: int):
 def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_empty: float = 0.9, dtype: str = "int8", nodata=None,
                    regression: bool = False, all_classes: bool = False, specific_class: Optional[int] = None, large_file: bool = False,
                    batch_size: int = 16, out_path=None, class_zero: bool = False, timing: Optional[dict] = None,
-                   batch_invariant: bool = False):
+                   batch_invariant: bool = False, tta=None):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -306,10 +346,13 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
              tile-by-tile loop), at the price of batch-1 plans on full grids
     large_file  the reference's int8 merge (predict.py:209-214,288-289,324-329): probabilities as around(p * 31) in int8 rasters, int8 hit
              counters, integer floor division -- same numbers as save_predictions(merge=True, large_file=True)
+    tta      None | "flips" | "d4" | a tuple of D4 codes (unet_amd/tta.py): test-time augmentation -- every window's probabilities (regression:
+             values) are the mean of g^-1(f(g(window))) over the set, computed before the merge; the hit counter still counts windows
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
     model = getattr(model, "model", model)
+    codes = tta_codes(tta, [(size, size)])
     rank, local_rank, world = _dist_ctx()
     dev = model._device
     gt, tags = None, {}
@@ -348,7 +391,8 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
 
     want = _want(regression, all_classes, specific_class)
     with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
-        out = _run_merge(model, places, MH, MW, regression, bool(large_file and not regression), rank, world, batch_size, make_input, want, timing)
+        out = _run_merge(model, places, MH, MW, regression, bool(large_file and not regression), rank, world, batch_size, make_input, want, timing,
+                         codes)
     if rank == 0 and out_path is not None:
         ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
         store_tif(out_path, out, ogt, tags, -9999 if regression else None, class_zero)
@@ -474,7 +518,8 @@ def _prefetcher(tiles, batches, sizes, device):
 
 def save_predictions(predict_model, predict_path, regression, merge=False, all_classes=False, specific_class=None, large_file=False,
                      AOI=None, year=None, validation_vision=True, class_zero=False, batch_size=16, timing: Optional[dict] = None,
-                     batch_invariant: bool = False):
+                     batch_invariant: bool = False, tta=None):
+    """tta: None | "flips" | "d4" | a tuple of D4 codes (see predict_raster and unet_amd/tta.py), merged and per-tile outputs alike"""
     rank, local_rank, world = _dist_ctx()
     dist = _dist()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
@@ -489,6 +534,7 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
         print(f"Started at: {time.strftime('%H:%M:%S')}  ({len(tiles)} tiles)")
     dtype = learn.dls.train_ds.dtype
     geos = [_geo(t) for t in tiles]
+    codes = tta_codes(tta, [(g[2], g[3]) for g in geos])
     dev = model._device
     C = model.n_out
     div2 = dtype == "int16"
@@ -538,7 +584,7 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
         want = _want(regression, all_classes, specific_class)
         try:
             with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):          # (see predict_raster)
-                out = _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch_size, make_input, want, timing)
+                out = _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch_size, make_input, want, timing, codes)
         finally:
             feed.close()
             if hasattr(pf, "close"):
@@ -567,24 +613,29 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     pf = _prefetcher(mtiles, batches, sizes, dev)
     zrows = [[0, 0, j, 0] for j in range(batch_size)]
     ztab = ops.window_table(zrows, dev)
+    acc = None if codes is None else _TTAAccumulator(model, codes, bool(regression))
     for first, n, buf in pf:
         d = pf.upload(buf, dev)
         _check_batch(0, n, d.shape[0], len(zrows))
         _check_windows(zrows[:d.shape[0]], d.shape[2], d.shape[3], d.shape[2], d.shape[3], sources=d.shape[0])
         wb = ops.WindowBatch(ops.WindowSource(d, div255_twice=div2), ztab, 0, d.shape[0], d.shape[2], d.shape[3])
+        h, w = d.shape[2], d.shape[3]
+        need_p = regression or all_classes or specific_class is not None
+        probs = torch.empty((n, C, h, w), dtype=torch.float32, device=dev) if need_p else None
+        amax = None if need_p else torch.empty((n, h, w), dtype=torch.int64, device=dev)
         with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
-            z = model.forward_windows(wb)
+            if acc is None:
+                z = model.forward_windows(wb)
+            else:                # TTA: the finalising accumulate writes the mean probabilities (values) / their argmax
+                acc.run(wb, n, probs, amax)
         if hasattr(pf, "done"):
             pf.done(buf)               # (the gather that reads the staging buffer has been issued)
-        zs = ops.TS(z.buf[:n], z.co, z.C)
-        if regression:       # predict.py:195-197: tile_preds[1] = raw outputs [1,H,W]
-            probs, amax = torch.empty((n, C, z.H, z.W), dtype=torch.float32, device=dev), None
-            ops.nhwc_to_nchw(zs, probs)
-        else:
-            need_p = all_classes or specific_class is not None
-            probs = torch.empty((n, C, z.H, z.W), dtype=torch.float32, device=dev) if need_p else None
-            amax = None if need_p else torch.empty((n, z.H, z.W), dtype=torch.int64, device=dev)
-            ops.softmax_argmax(zs, probs, amax)
+        if acc is None:
+            zs = ops.TS(z.buf[:n], z.co, z.C)
+            if regression:       # predict.py:195-197: tile_preds[1] = raw outputs [1,H,W]
+                ops.nhwc_to_nchw(zs, probs)
+            else:
+                ops.softmax_argmax(zs, probs, amax)
         outs = (probs if probs is not None else amax.to(torch.uint8)).cpu().numpy()
         for j in range(n):
             t = mtiles[first + j]

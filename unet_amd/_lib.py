@@ -182,6 +182,9 @@ _sig = {
     "unet_dice_counts": (i, [vp, vp, ll, i, vp, vp]),
     "unet_warp_affine": (i, [vp, vp, i, i, i, i, c_float_p, i, i, f, vp]),
     "unet_warp_affine_mask": (i, [vp, vp, i, i, i, i, c_float_p, i, C.c_double, vp]),
+    "unet_window_gather_oriented": (i, [vp, i, i, ll, ll, i, vp, i, i, i, i, vp, i, i, i, i, vp]),
+    "unet_nchw_to_nhwc_oriented": (i, [vp, vp, i, i, i, i, i, i, i, i, vp]),
+    "unet_tta_accumulate": (i, [vp, i, i, i, i, i, i, i, i, i, vp, i, i, vp, vp, vp]),
 }
 # bf16-storage twins: same argument lists (every tensor is a void pointer on this side)
 for _n in ("bn_stats", "affine_act", "bn_bwd_reduce", "bn_bwd_apply", "maxpool3x3s2", "maxpool3x3s2_bwd", "avgpool2_ceil",

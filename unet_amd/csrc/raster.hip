@@ -10,6 +10,10 @@
 //   unet_mosaic_accumulate_windows  predict.py:193-203 softmax + predict.py:284-292 placement of a whole BATCH of windows in one launch,
 //                                contributions to one mosaic pixel added in window order (deterministic: no atomics)
 //   unet_mosaic_finalize_rows    predict.py:306-334 divide by the hit counter, argmax (classification) / -9999 fill (regression)
+// Test-time augmentation (TTA) of the same path: the 8 symmetries of the square (D4 codes, unet_hip.h) as exact index permutations,
+//   unet_window_gather_oriented  the gather above writing g(window)
+//   unet_nchw_to_nhwc_oriented   the same for an fp32 NCHW batch (Learner.predict / get_preds)
+//   unet_tta_accumulate          g^-1(softmax(logits)) [or g^-1(raw values)] summed per window in launch order, / k at the last code
 // All of it is HBM-bound byte / float traffic: one pass over the data each, coalesced along x.
 #include "common.h"
 
@@ -71,6 +75,168 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const S* __restrict_
             if (div2) v = __fdiv_rn(v, 255.0f);
             st_act(o + c, __fdiv_rn(v, 255.0f));
         }
+    }
+}
+
+// ---- D4 codes (test-time augmentation).  Output pixel (i, k) of g(x) is x[r][c] with (r, c) = d4_src(g, i, k); codes 4..7 need H == W.
+//   0 x   1 flip(x, [-1])   2 flip(x, [-2])   3 flip(x, [-2, -1])   4 x^T   5 rot90(x, 1)   6 rot90(x, -1)   7 flip(x^T, [-2, -1])
+// inverses: 5 <-> 6, every other code is its own
+__device__ __forceinline__ void d4_src(int g, int i, int k, int H, int W, int& r, int& c) {
+    switch (g) {
+        case 1: r = i; c = W - 1 - k; break;
+        case 2: r = H - 1 - i; c = k; break;
+        case 3: r = H - 1 - i; c = W - 1 - k; break;
+        case 4: r = k; c = i; break;
+        case 5: r = k; c = W - 1 - i; break;
+        case 6: r = H - 1 - k; c = i; break;
+        case 7: r = H - 1 - k; c = W - 1 - i; break;
+        default: r = i; c = k; break;
+    }
+}
+constexpr int d4_inverse(int g) { return g == 5 ? 6 : (g == 6 ? 5 : g); }
+
+// x[j][y][x][co + c] = the sample window_gather_kernel would write at d4_src(orient, y, x): same cast, same division(s)
+template <typename S, typename T>
+__global__ __launch_bounds__(256) void window_gather_oriented_kernel(const S* __restrict__ r, int Cb, long long src_stride, long long band_stride,
+                                                                     int row_stride, const int* __restrict__ win, int n, int th, int tw,
+                                                                     int div2, int orient, T* __restrict__ x, int x_cs, int x_co) {
+    const long long per = (long long)th * tw, total = per * n;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int j = (int)(i / per);
+        const long long p = i - (long long)j * per;
+        const int y = (int)(p / tw), xx = (int)(p - (long long)y * tw);
+        int sy, sx;
+        d4_src(orient, y, xx, th, tw, sy, sx);
+        const int y0 = win[4 * j], x0 = win[4 * j + 1], src = win[4 * j + 2];
+        const S* s = r + (size_t)src * src_stride + (size_t)(y0 + sy) * row_stride + x0 + sx;
+        T* o = x + (size_t)i * x_cs + x_co;
+        for (int c = 0; c < Cb; ++c) {
+            float v = (float)as_i32(s[(size_t)c * band_stride]);
+            if (div2) v = __fdiv_rn(v, 255.0f);
+            st_act(o + c, __fdiv_rn(v, 255.0f));
+        }
+    }
+}
+
+// y[nn][i][k][co + c] = x[nn][c][d4_src(orient, i, k)]: the oriented input of Learner.predict / get_preds
+template <typename T>
+__global__ __launch_bounds__(256) void nchw_to_nhwc_oriented_kernel(const float* __restrict__ x, T* __restrict__ y, int y_cs, int y_co, int N,
+                                                                    int C, int H, int W, int orient) {
+    const long long HW = (long long)H * W, total = (long long)N * HW;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long nn = i / HW, p = i - nn * HW;
+        const int yy = (int)(p / W), xx = (int)(p - (long long)yy * W);
+        int sy, sx;
+        d4_src(orient, yy, xx, H, W, sy, sx);
+        const float* s = x + (size_t)nn * C * HW + (size_t)sy * W + sx;
+        T* o = y + (size_t)i * y_cs + y_co;
+        for (int c = 0; c < C; ++c) st_act(o + c, s[(size_t)c * HW]);
+    }
+}
+
+// Thread (j, y, x) owns accumulator pixel acc[j][y][x][:]: it reads the logits of window j, produced under code `orient`, at
+// d4_src(inverse(orient), y, x) -- i.e. g^-1 of the network's output -- and stores (first) or adds its softmax (mode 0: exactly the
+// arithmetic of softmax_argmax_kernel) or raw values (mode 1).  finalize_k > 0 (the last code of a set of k): the sum is divided by k
+// with one rounded division and kept in acc; probs (NCHW) and argmax (int64, first maximum) are written when given.  One thread per
+// pixel, codes in launch order: no atomics, deterministic.
+__device__ __forceinline__ void tta_pixel(const float* zp, int C, int mode, int first, float* __restrict__ a, int finalize_k,
+                                          float* __restrict__ probs, int64_t* __restrict__ amax, int j, long long per, long long p, long long i) {
+    float mx = 0.f, s = 0.f;
+    if (mode == 0) {
+        mx = zp[0];
+        for (int c = 1; c < C; ++c) mx = fmaxf(mx, zp[c]);
+        for (int c = 0; c < C; ++c) s += expf(zp[c] - mx);
+    }
+    float best = -1.f;
+    int bi = 0;
+    for (int c = 0; c < C; ++c) {
+        float v = mode == 0 ? expf(zp[c] - mx) / s : zp[c];
+        if (!first) v = __fadd_rn(a[c], v);
+        if (finalize_k > 0) {
+            v = __fdiv_rn(v, (float)finalize_k);
+            if (probs) probs[((size_t)j * C + c) * per + p] = v;
+            if (v > best) { best = v; bi = c; }
+        }
+        a[c] = v;
+    }
+    if (finalize_k > 0 && amax) amax[i] = bi;
+}
+
+__global__ __launch_bounds__(256) void tta_accumulate_kernel(const float* __restrict__ z, int z_cs, int z_co, int n, int C, int th, int tw,
+                                                             int orient, int mode, int first, float* __restrict__ acc, int acc_cs,
+                                                             int finalize_k, float* __restrict__ probs, int64_t* __restrict__ amax) {
+    const long long per = (long long)th * tw, total = per * n;
+    const int inv = d4_inverse(orient);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int j = (int)(i / per);
+        const long long p = i - (long long)j * per;
+        const int y = (int)(p / tw), xx = (int)(p - (long long)y * tw);
+        int sy, sx;
+        d4_src(inv, y, xx, th, tw, sy, sx);
+        tta_pixel(z + ((size_t)j * per + (size_t)sy * tw + sx) * z_cs + z_co, C, mode, first, acc + (size_t)i * acc_cs, finalize_k, probs, amax,
+                  j, per, p, i);
+    }
+}
+
+// ---- codes 4..7 read across rows: staged through an LDS tile (cdna_hip_programming.md, Guidelines 2-4).  One workgroup per 32 x 32 output
+// tile of one window.  Phase 1 walks the tile with ly fastest -- for codes 4..7 the SOURCE column follows the output row, so these reads
+// are coalesced -- and parks the Cv values of every pixel at lds[(lx * 33 + ly) * Cv] (33: no bank conflicts in phase 2); phase 2 walks
+// it with lx fastest and does the coalesced stores.  Same arithmetic as the direct kernels, in the same thread-per-pixel order.
+constexpr int TT = 32;
+constexpr int TT_MAXC = 15;         // 32 * 33 * 15 floats = 63360 bytes of LDS: within the 64 KiB a launch may ask for without attributes
+
+template <typename S, typename T>
+__global__ __launch_bounds__(256) void window_gather_oriented_lds_kernel(const S* __restrict__ r, int Cb, long long src_stride, long long band_stride,
+                                                                         int row_stride, const int* __restrict__ win, int th, int tw, int div2,
+                                                                         int orient, int tiles_x, int tiles, T* __restrict__ x, int x_cs, int x_co) {
+    extern __shared__ float lds[];
+    const int j = blockIdx.x / tiles, t = blockIdx.x - j * tiles;
+    const int Y0 = (t / tiles_x) * TT, X0 = (t % tiles_x) * TT;
+    const int y0 = win[4 * j], x0 = win[4 * j + 1], src = win[4 * j + 2];
+    for (int e = threadIdx.x; e < TT * TT; e += 256) {
+        const int ly = e % TT, lx = e / TT, y = Y0 + ly, xx = X0 + lx;
+        if (y >= th || xx >= tw) continue;
+        int sy, sx;
+        d4_src(orient, y, xx, th, tw, sy, sx);
+        const S* s = r + (size_t)src * src_stride + (size_t)(y0 + sy) * row_stride + x0 + sx;
+        for (int c = 0; c < Cb; ++c) {
+            float v = (float)as_i32(s[(size_t)c * band_stride]);
+            if (div2) v = __fdiv_rn(v, 255.0f);
+            lds[(lx * (TT + 1) + ly) * Cb + c] = __fdiv_rn(v, 255.0f);
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < TT * TT; e += 256) {
+        const int lx = e % TT, ly = e / TT, y = Y0 + ly, xx = X0 + lx;
+        if (y >= th || xx >= tw) continue;
+        T* o = x + ((size_t)j * th * tw + (size_t)y * tw + xx) * x_cs + x_co;
+        for (int c = 0; c < Cb; ++c) st_act(o + c, lds[(lx * (TT + 1) + ly) * Cb + c]);
+    }
+}
+
+__global__ __launch_bounds__(256) void tta_accumulate_lds_kernel(const float* __restrict__ z, int z_cs, int z_co, int C, int th, int tw,
+                                                                 int orient, int mode, int first, float* __restrict__ acc, int acc_cs,
+                                                                 int finalize_k, float* __restrict__ probs, int64_t* __restrict__ amax,
+                                                                 int tiles_x, int tiles) {
+    extern __shared__ float lds[];
+    const int j = blockIdx.x / tiles, t = blockIdx.x - j * tiles;
+    const int Y0 = (t / tiles_x) * TT, X0 = (t % tiles_x) * TT;
+    const long long per = (long long)th * tw;
+    const int inv = d4_inverse(orient);
+    for (int e = threadIdx.x; e < TT * TT; e += 256) {
+        const int ly = e % TT, lx = e / TT, y = Y0 + ly, xx = X0 + lx;
+        if (y >= th || xx >= tw) continue;
+        int sy, sx;
+        d4_src(inv, y, xx, th, tw, sy, sx);
+        const float* zp = z + ((size_t)j * per + (size_t)sy * tw + sx) * z_cs + z_co;
+        for (int c = 0; c < C; ++c) lds[(lx * (TT + 1) + ly) * C + c] = zp[c];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < TT * TT; e += 256) {
+        const int lx = e % TT, ly = e / TT, y = Y0 + ly, xx = X0 + lx;
+        if (y >= th || xx >= tw) continue;
+        const long long p = (long long)y * tw + xx, i = (long long)j * per + p;
+        tta_pixel(lds + (lx * (TT + 1) + ly) * C, C, mode, first, acc + (size_t)i * acc_cs, finalize_k, probs, amax, j, per, p, i);
     }
 }
 
@@ -257,6 +423,78 @@ extern "C" int unet_window_gather(const void* src, int rtype, int bands, long lo
                                                   src_stride, band_stride, row_stride, windows, n, th, tw, div255_twice, (unet_bf16*)x, x_cs,
                                                   x_co));
     }
+    UNET_CHECK_LAUNCH();
+    return UNET_OK;
+}
+
+static bool d4_ok(int orient, int h, int w) { return orient >= 0 && orient < 8 && (orient < 4 || h == w); }
+
+extern "C" int unet_window_gather_oriented(const void* src, int rtype, int bands, long long src_stride, long long band_stride, int row_stride,
+                                           const int32_t* windows, int n, int th, int tw, int div255_twice, void* x, int x_cs, int x_co,
+                                           int dtype, int orient, void* stream) {
+    UNET_CHECK_ARG(src && windows && x && bands > 0 && n > 0 && th > 0 && tw > 0 && row_stride >= tw, "window_gather_oriented: bad args");
+    UNET_CHECK_ARG(x_co >= 0 && x_co + bands <= x_cs && (dtype == UNET_F32 || dtype == UNET_BF16), "window_gather_oriented: bad slice / dtype");
+    UNET_CHECK_ARG(d4_ok(orient, th, tw), "window_gather_oriented: code %d on %d x %d windows (0..7; 4..7 need square windows)", orient, th, tw);
+    const int tiles_x = (tw + TT - 1) / TT, tiles = tiles_x * ((th + TT - 1) / TT);
+    if (orient >= 4 && bands <= TT_MAXC && (long long)n * tiles <= 0x7fffffffLL) {
+        const size_t shm = sizeof(float) * TT * (TT + 1) * bands;
+        if (dtype == UNET_F32) {
+            RASTER_DISPATCH(rtype, hipLaunchKernelGGL((window_gather_oriented_lds_kernel<S, float>), dim3((unsigned)(n * tiles)), dim3(256), shm, ST,
+                                                      (const S*)src, bands, src_stride, band_stride, row_stride, windows, th, tw, div255_twice,
+                                                      orient, tiles_x, tiles, (float*)x, x_cs, x_co));
+        } else {
+            RASTER_DISPATCH(rtype, hipLaunchKernelGGL((window_gather_oriented_lds_kernel<S, unet_bf16>), dim3((unsigned)(n * tiles)), dim3(256), shm,
+                                                      ST, (const S*)src, bands, src_stride, band_stride, row_stride, windows, th, tw,
+                                                      div255_twice, orient, tiles_x, tiles, (unet_bf16*)x, x_cs, x_co));
+        }
+        UNET_CHECK_LAUNCH();
+        return UNET_OK;
+    }
+    const int grid = ew_grid((long long)n * th * tw, 256);
+    if (dtype == UNET_F32) {
+        RASTER_DISPATCH(rtype, hipLaunchKernelGGL((window_gather_oriented_kernel<S, float>), dim3(grid), dim3(256), 0, ST, (const S*)src, bands,
+                                                  src_stride, band_stride, row_stride, windows, n, th, tw, div255_twice, orient, (float*)x, x_cs,
+                                                  x_co));
+    } else {
+        RASTER_DISPATCH(rtype, hipLaunchKernelGGL((window_gather_oriented_kernel<S, unet_bf16>), dim3(grid), dim3(256), 0, ST, (const S*)src,
+                                                  bands, src_stride, band_stride, row_stride, windows, n, th, tw, div255_twice, orient,
+                                                  (unet_bf16*)x, x_cs, x_co));
+    }
+    UNET_CHECK_LAUNCH();
+    return UNET_OK;
+}
+
+extern "C" int unet_nchw_to_nhwc_oriented(const float* x, void* y, int y_cs, int y_co, int N, int C, int H, int W, int dtype, int orient,
+                                          void* stream) {
+    UNET_CHECK_ARG(x && y && N > 0 && C > 0 && H > 0 && W > 0 && y_co >= 0 && y_co + C <= y_cs && (dtype == UNET_F32 || dtype == UNET_BF16),
+                   "nchw_to_nhwc_oriented: bad args");
+    UNET_CHECK_ARG(d4_ok(orient, H, W), "nchw_to_nhwc_oriented: code %d on %d x %d images (0..7; 4..7 need square images)", orient, H, W);
+    const int grid = ew_grid((long long)N * H * W, 256);
+    if (dtype == UNET_F32)
+        hipLaunchKernelGGL((nchw_to_nhwc_oriented_kernel<float>), dim3(grid), dim3(256), 0, ST, x, (float*)y, y_cs, y_co, N, C, H, W, orient);
+    else
+        hipLaunchKernelGGL((nchw_to_nhwc_oriented_kernel<unet_bf16>), dim3(grid), dim3(256), 0, ST, x, (unet_bf16*)y, y_cs, y_co, N, C, H, W,
+                           orient);
+    UNET_CHECK_LAUNCH();
+    return UNET_OK;
+}
+
+extern "C" int unet_tta_accumulate(const float* z, int z_cs, int z_co, int n, int C, int th, int tw, int orient, int mode, int first,
+                                   float* acc, int acc_cs, int finalize_k, float* probs, int64_t* argmax, void* stream) {
+    UNET_CHECK_ARG(z && acc && n > 0 && C > 0 && C <= MAXC && th > 0 && tw > 0 && z_co >= 0 && z_co + C <= z_cs && acc_cs >= C,
+                   "tta_accumulate: bad args");
+    UNET_CHECK_ARG((mode == 0 || mode == 1) && (first == 0 || first == 1) && finalize_k >= 0 && (finalize_k > 0 || (!probs && !argmax)),
+                   "tta_accumulate: bad mode / first / finalize");
+    UNET_CHECK_ARG(d4_ok(orient, th, tw), "tta_accumulate: code %d on %d x %d windows (0..7; 4..7 need square windows)", orient, th, tw);
+    const int tiles_x = (tw + TT - 1) / TT, tiles = tiles_x * ((th + TT - 1) / TT);
+    if (orient >= 4 && C <= TT_MAXC && (long long)n * tiles <= 0x7fffffffLL) {
+        hipLaunchKernelGGL(tta_accumulate_lds_kernel, dim3((unsigned)(n * tiles)), dim3(256), sizeof(float) * TT * (TT + 1) * C, ST, z, z_cs, z_co, C,
+                           th, tw, orient, mode, first, acc, acc_cs, finalize_k, probs, (int64_t*)argmax, tiles_x, tiles);
+        UNET_CHECK_LAUNCH();
+        return UNET_OK;
+    }
+    hipLaunchKernelGGL(tta_accumulate_kernel, dim3(ew_grid((long long)n * th * tw, 256)), dim3(256), 0, ST, z, z_cs, z_co, n, C, th, tw, orient,
+                       mode, first, acc, acc_cs, finalize_k, probs, (int64_t*)argmax);
     UNET_CHECK_LAUNCH();
     return UNET_OK;
 }

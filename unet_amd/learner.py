@@ -880,16 +880,18 @@ class Learner:
         return out
 
     @torch.no_grad()
-    def get_preds(self, dl=None, with_input=False, with_decoded=False):
+    def get_preds(self, dl=None, with_input=False, with_decoded=False, tta=None):
+        """tta: None | "flips" | "d4" | a tuple of D4 codes (unet_amd/tta.py): every batch's predictions are the mean of
+        g^-1(softmax(f(g(x)))) (regression: of g^-1(f(g(x)))) over the set, the decoded argmax that of the mean"""
         dl = dl or self.dls.valid
         self.model.eval()
         xs, ps, ys, ds = [], [], [], []
         for xb, yb in dl:
             if self.regression:
-                vals = self.model.predict_values(xb)      # decoded == preds: no activation (train.py:90-95)
+                vals = self.model.predict_values(xb, tta=tta)      # decoded == preds: no activation (train.py:90-95)
                 ps.append(vals)
             else:
-                probs, amax = self.model.predict_probs(xb)
+                probs, amax = self.model.predict_probs(xb, tta=tta)
                 ps.append(probs); ds.append(amax)
             if with_input:
                 xs.append(xb)
@@ -903,16 +905,44 @@ class Learner:
             res = (self._to_host(xs),) + res
         return res
 
-    def predict(self, item, rm_type_tfms=None, with_input=False):
+    def predict(self, item, rm_type_tfms=None, with_input=False, tta=None):
         """(decoded mask, argmax [H,W], per-class probabilities [C,H,W]) for one tile (path or [C,H,W] array); in regression
         mode the 2-tuple (decoded, preds) of ``Learner_adjust.predict`` (train.py:87-95), both [1,H,W].  The reference's per-tile loop
-        (predict.py:191-193); predict.save_predictions batches 16 tiles instead."""
+        (predict.py:191-193); predict.save_predictions batches 16 tiles instead.  tta: as in get_preds."""
         dl = self.dls.test_dl([item])
-        preds, _, dec = self.get_preds(dl=dl, with_decoded=True)
+        preds, _, dec = self.get_preds(dl=dl, with_decoded=True, tta=tta)
         if self.regression:
             return dec[0], preds[0]
         res = dec[0], dec[0], preds[0]
         return res
+
+    def tta(self, ds_idx=1, dl=None, n=4, item_tfms=None, batch_tfms=None, beta=0.25, use_max=False):
+        """fastai ``Learner.tta`` with deterministic passes: ``preds`` is the plain pass, the augmented passes are the D4 codes 1..n of
+        unet_amd/tta.py (flips first, then transposes and quarter turns: n <= 7, and n <= 3 for non-square tiles).  ``aug_preds`` is
+        their mean (one device accumulate, get_preds(tta=(1, ..., n))) or, with use_max, their element-wise max.  Returns
+        (torch.lerp(aug_preds, preds, beta), targs); ((aug_preds, preds), targs) for beta=None; with use_max the element-wise max of
+        preds and aug_preds."""
+        if item_tfms is not None or batch_tfms is not None:
+            raise NotImplementedError("tta: passes are the deterministic D4 codes 1..n, not draws of item_tfms / batch_tfms")
+        if not 1 <= int(n) <= 7:
+            raise ValueError(f"tta: n={n} augmented passes; the D4 group has 7 besides the identity (n <= 3 for non-square tiles: flips)")
+        if dl is None:
+            # fastai: dls[ds_idx].new(shuffled=False, drop_last=False) -- the validation loader is that already
+            dl = self.dls.valid if ds_idx == 1 else DataLoader(self.dls.train_ds, self.dls.bs, False, self.dls.device)
+            if dl is None:
+                raise ValueError(f"tta: no validation set (ds_idx={ds_idx})")
+        codes = tuple(range(1, int(n) + 1))
+        if use_max:
+            aug = None
+            for c in codes:
+                p = self.get_preds(dl=dl, tta=(c,))[0]
+                aug = p if aug is None else torch.maximum(aug, p)
+        else:
+            aug = self.get_preds(dl=dl, tta=codes)[0]
+        preds, targs = self.get_preds(dl=dl)
+        if use_max:
+            return torch.maximum(preds, aug), targs
+        return ((aug, preds) if beta is None else torch.lerp(aug, preds, beta)), targs
 
     # -- learning-rate finder (fastai callback/schedule.py LRFinder + Learner.lr_find; reference utils.py:150-167)
     def lr_find(self, start_lr=1e-7, end_lr=10, num_it=100, stop_div=True, show_plot=False, suggest_funcs=("valley",)):

@@ -261,17 +261,21 @@ class HipDynamicUnet(nn.Module):
         return r
 
     # ------------------------------------------------------------------ programs
-    def _hip_forward(self, x: torch.Tensor, training: bool) -> TS:
-        """x: [B, n_in, H, W] fp32 (device).  Returns the logits slice (NHWC)."""
+    def _hip_forward(self, x: torch.Tensor, training: bool, orient: Optional[int] = None) -> TS:
+        """x: [B, n_in, H, W] fp32 (device).  Returns the logits slice (NHWC).  orient: a D4 code (unet_amd/tta.py) -- the network sees
+        g(x), written by the oriented gather / staging kernel (the logits are those of g(x), NOT mapped back)."""
         if isinstance(x, ops.WindowBatch):      # windows of an integer raster / staged tiles: cut + scaled on the device (predict_raster)
             assert x.src.C == self.n_in, (x.src.C, self.n_in)
             N, H, W = x.n, x.th, x.tw
-            put = x.write
+            put = x.write if orient is None else (lambda buf, at, _x=x: _x.write(buf, at, orient))
         else:
             assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == self.n_in, x.shape
             x = x.contiguous()
             N, _, H, W = x.shape
-            put = lambda buf, at, _x=x: ops.nchw_to_nhwc(_x, ops.TS(buf, 0, buf.shape[3]), at=at)
+            if orient is None:
+                put = lambda buf, at, _x=x: ops.nchw_to_nhwc(_x, ops.TS(buf, 0, buf.shape[3]), at=at)
+            else:
+                put = lambda buf, at, _x=x: ops.nchw_to_nhwc_oriented(_x, buf, at, orient)
         ctx = self.ctx
         ctx.training = training
         ctx.main_stream = None
@@ -554,28 +558,55 @@ class HipDynamicUnet(nn.Module):
         return loss
 
     @torch.no_grad()
-    def predict_values(self, x: torch.Tensor) -> torch.Tensor:
-        """eval-mode forward, raw outputs [B,n_out,H,W] (regression: no activation, train.py:90-95)."""
+    def predict_values(self, x: torch.Tensor, tta=None) -> torch.Tensor:
+        """eval-mode forward, raw outputs [B,n_out,H,W] (regression: no activation, train.py:90-95).  tta: None | "flips" | "d4" | codes
+        (unet_amd/tta.py): the mean of g^-1(f(g(x))) over the set, in code order."""
         x = x.to(self._device, torch.float32)
+        if tta is not None:
+            return self._predict_tta(x, tta, True, True, False)[0]
         z = self._hip_forward(x, False)
         out = torch.empty((z.N, z.C, z.H, z.W), dtype=torch.float32, device=self._device)
         ops.nhwc_to_nchw(z, out)
         return out
 
     @torch.no_grad()
-    def predict_probs(self, x: torch.Tensor, want_probs=True, want_argmax=True):
-        """eval-mode forward + softmax(dim=1) + argmax: what Learner.predict returns per tile (predict.py:193-203,232)."""
+    def predict_probs(self, x: torch.Tensor, want_probs=True, want_argmax=True, tta=None):
+        """eval-mode forward + softmax(dim=1) + argmax: what Learner.predict returns per tile (predict.py:193-203,232).  tta: None | "flips"
+        | "d4" | codes (unet_amd/tta.py): probabilities = the mean of g^-1(softmax(f(g(x)))) over the set, argmax of that mean."""
         x = x.to(self._device, torch.float32)
+        if tta is not None:
+            return self._predict_tta(x, tta, False, want_probs, want_argmax)
         z = self._hip_forward(x, False)
         probs = torch.empty((z.N, z.C, z.H, z.W), dtype=torch.float32, device=self._device) if want_probs else None
         amax = torch.empty((z.N, z.H, z.W), dtype=torch.int64, device=self._device) if want_argmax else None
         ops.softmax_argmax(z, probs, amax)
         return probs, amax
 
+    def _predict_tta(self, x: torch.Tensor, tta, raw: bool, want_probs: bool, want_argmax: bool):
+        """k eager forwards of the oriented batch, each mapped back and added in code order on the device (unet_tta_accumulate); the
+        last launch divides by k and writes the NCHW output / argmax"""
+        from .tta import parse
+        N, _, H, W = x.shape
+        codes = parse(tta, [(H, W)])
+        acc = torch.empty((N, H, W, ops.rup4(self.n_out)), dtype=torch.float32, device=self._device)
+        probs = torch.empty((N, self.n_out, H, W), dtype=torch.float32, device=self._device) if want_probs else None
+        amax = torch.empty((N, H, W), dtype=torch.int64, device=self._device) if want_argmax and not raw else None
+        for i, g in enumerate(codes):
+            z = self._hip_forward(x, False, orient=g)
+            last = i == len(codes) - 1
+            ops.tta_accumulate(z, N, g, raw, i == 0, acc, len(codes) if last else 0, probs if last else None, amax if last else None)
+        return probs, amax
+
     @torch.no_grad()
     def forward_windows(self, wb: "ops.WindowBatch") -> TS:
         """eval-mode forward of a batch of raster windows; returns the fp32 NHWC logits slice (valid until the next forward)"""
         return self._hip_forward(wb, False)
+
+    @torch.no_grad()
+    def forward_windows_oriented(self, wb: "ops.WindowBatch", orient: int) -> TS:
+        """forward_windows of g(window) for every window of the batch, g the D4 code `orient` (unet_amd/tta.py); the logits are those of
+        the oriented windows (unet_tta_accumulate maps them back)"""
+        return self._hip_forward(wb, False, orient=int(orient))
 
     def memory_bytes(self) -> int:
         return self.ctx.bytes_allocated() + 2 * self.flat_param.numel() * 4

@@ -815,8 +815,12 @@ class WindowBatch:
     th: int
     tw: int
 
-    def write(self, dst_buf: torch.Tensor, at: int):
-        window_gather(self.src, self.table, self.first, self.n, self.th, self.tw, dst_buf, at)
+    def write(self, dst_buf: torch.Tensor, at: int, orient: Optional[int] = None):
+        """orient None: the plain gather; a D4 code (unet_amd/tta.py): every window written as g(window), code 0 included"""
+        if orient is None:
+            window_gather(self.src, self.table, self.first, self.n, self.th, self.tw, dst_buf, at)
+        else:
+            window_gather_oriented(self.src, self.table, self.first, self.n, self.th, self.tw, dst_buf, at, orient)
 
 
 def raster_nodata_zero(src: WindowSource, nodata: float):
@@ -842,6 +846,45 @@ def window_gather(src: WindowSource, table: torch.Tensor, first: int, n: int, th
     check(lib.unet_window_gather(src.data.data_ptr(), src.rtype, src.C, src.src_stride, src.H * src.W, src.W,
                                  table.data_ptr() + 16 * first, n, th, tw, src.div2, dst_buf.data_ptr(), dst_buf.shape[3], at, dt,
                                  _stream()), "window_gather")
+
+
+def window_gather_oriented(src: WindowSource, table: torch.Tensor, first: int, n: int, th: int, tw: int, dst_buf: torch.Tensor, at: int,
+                           orient: int):
+    """window_gather with every window written as g(window), g the D4 code `orient` (codes 4..7 need th == tw)"""
+    assert dst_buf.dim() == 4 and dst_buf.shape[0] >= n and tuple(dst_buf.shape[1:3]) == (th, tw) and dst_buf.is_contiguous()
+    assert 0 <= first and first + n <= table.shape[0]
+    dt = L.BF16 if dst_buf.dtype == torch.bfloat16 else L.F32
+    check(lib.unet_window_gather_oriented(src.data.data_ptr(), src.rtype, src.C, src.src_stride, src.H * src.W, src.W,
+                                          table.data_ptr() + 16 * first, n, th, tw, src.div2, dst_buf.data_ptr(), dst_buf.shape[3], at, dt,
+                                          int(orient), _stream()), "window_gather_oriented")
+
+
+def nchw_to_nhwc_oriented(x: torch.Tensor, dst_buf: torch.Tensor, at: int, orient: int):
+    """fp32 NCHW x [N, C, H, W] -> channels [at, at + C) of the NHWC buffer dst_buf [>= N, H, W, cs] (fp32 or bf16), image n written
+    as g(x[n]), g the D4 code `orient`"""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
+    N, C_, H, W = x.shape
+    assert dst_buf.dim() == 4 and dst_buf.shape[0] >= N and tuple(dst_buf.shape[1:3]) == (H, W) and dst_buf.is_contiguous()
+    assert at >= 0 and at + C_ <= dst_buf.shape[3]
+    dt = L.BF16 if dst_buf.dtype == torch.bfloat16 else L.F32
+    check(lib.unet_nchw_to_nhwc_oriented(x.data_ptr(), dst_buf.data_ptr(), dst_buf.shape[3], at, N, C_, H, W, dt, int(orient), _stream()),
+          "nchw_to_nhwc_oriented")
+
+
+def tta_accumulate(z: TS, n: int, orient: int, raw: bool, first: bool, acc: torch.Tensor, finalize_k: int = 0,
+                   probs: Optional[torch.Tensor] = None, amax: Optional[torch.Tensor] = None):
+    """acc [>= n, H, W, cs] fp32 (channels [0, C)) = (first ? 0 : acc) + g^-1(softmax(z)) -- raw=True: g^-1(z) -- for the fp32 NHWC logits
+    z of n windows produced under code g = orient.  finalize_k > 0 (last code of a set of k): acc /= k in place; probs (NCHW fp32
+    [n, C, H, W]) and amax (int64 [n, H, W]) are written when given."""
+    _need_f32("tta_accumulate", z)
+    assert z.N >= n > 0
+    assert acc.dtype == torch.float32 and acc.is_contiguous() and acc.dim() == 4 and acc.shape[0] >= n
+    assert tuple(acc.shape[1:3]) == (z.H, z.W) and acc.shape[3] >= z.C
+    assert finalize_k > 0 or (probs is None and amax is None)
+    assert probs is None or (probs.dtype == torch.float32 and probs.is_contiguous() and tuple(probs.shape) == (n, z.C, z.H, z.W))
+    assert amax is None or (amax.dtype == torch.int64 and amax.is_contiguous() and tuple(amax.shape) == (n, z.H, z.W))
+    check(lib.unet_tta_accumulate(z.ptr, z.cs, z.co, n, z.C, z.H, z.W, int(orient), int(bool(raw)), int(bool(first)), acc.data_ptr(),
+                                  acc.shape[3], int(finalize_k), _p(probs), _p(amax), _stream()), "tta_accumulate")
 
 
 # ------------------------------------------------------------------ training feed (csrc/raster.hip: unet_tiles_stage / unet_mask_stage)
