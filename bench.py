@@ -2,19 +2,23 @@
 """Headline benchmark: 512x512 tiles/s, forward + backward + optimizer step, 4-channel -> 5-class xresnet34
 DynamicUnet (BASELINE.json configs[1]: batch 16 per MI355X; configs[2]: the same per GPU, tile-DDP over N GPUs).
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 Prints ONE JSON line on rank 0.  `value` = tiles processed by all ranks / wall time of the K timed steps (max over
 ranks), inputs resident in HBM.  `roofline` is the dominant kernel (the fp32 form of the 256-pixel implicit-GEMM conv tile,
 its large-layer launches: forward and input-gradient of every wide 3x3 layer): summed algorithmic FLOPs / summed launch durations measured with
 events on the launch stream inside the timed region; `roofline.traffic` comes from the committed counter summary it names
-(`traffic_source`, `traffic_code`, `traffic_code_current`).  `cpu_baseline` = the torch-CPU oracle of the same step on this host's cores, on a
+(`traffic_source`, `traffic_code`, `traffic_code_current`).  Every rank reports its own clock and the time its compute stream waited for
+the gradient all-reduce in `devices`.
+
+A plain run stops there: set-up, warm-up, the K timed steps, --dump-outputs, the line.  What follows takes runs of its own and is
+measured only with --full, after the headline.  `cpu_baseline` = the torch-CPU oracle of the same step on this host's cores, on a
 bounded sample (rank 0, N=1 only).  The N=1 run also carries `secondary`, every entry in its own try: the bf16-storage variant of configs[1]
 (value un-probed, roofline from a second, probed run), predict at batch 16 / 1, `Learner.predict` per tile, configs[0] (cfg1), configs[3] (cfg4: xresnet50 8 -> 10,
 1024 x 1024, fp32), the step with self-attention on (the reference's shipped default), configs[4] (cfg5: predict.predict_raster over a
 20000 x 20000 raster) in fp32 and bf16 storage, `predict_files`: predict.save_predictions(merge=True) over 400 tile files, and `fit_files`: Learner.fit_one_cycle over tile FILES
 through the product loader next to the resident-batch rate.  N > 1 runs add cfg5 over all ranks behind a watchdog that prints the headline with the failure
-recorded and exits non-zero.  Every rank reports its own clock and the time its compute stream waited for the gradient all-reduce in `devices`.
+recorded and exits non-zero.
 """
 from __future__ import annotations
 
@@ -524,8 +528,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=16, help="tiles per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (bf16 step, predict, cfg1, cfg5) of the N=1 run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the CPU baseline and the secondary measurements (N=1: bf16 step, predict, cfg1, "
+                         "cfg4, self-attention, cfg5, file-fed predict and fit; N>1: cfg5 over all ranks)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary measurements")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
                     help="f32 (default): the parity path, the headline.  bf16: bf16 storage / fp32 accumulate variant of configs[1]")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -533,6 +540,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    secondary = args.full and not args.no_secondary and args.dtype == "f32"
+    cpu_base = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))          # this process never initialises the GPU
@@ -598,7 +607,7 @@ def main():
             "dist_backend": (dist.get_backend() if world > 1 else None),
             "devices": devices,
         }
-        if world == 1 and not args.no_secondary and args.dtype == "f32":
+        if world == 1 and secondary:
             # measured in this same process, after the headline: the other BASELINE configurations and the bf16-storage variant of configs[1].
             # Every entry runs in its own try: a failure there is recorded in the entry and the headline line is still printed.
             sec = {}
@@ -677,10 +686,10 @@ def main():
             guarded("fit_files", "fit_one_cycle from tile files through the product loader (uncompressed + LZW + JPEG, fp32 + bf16)",
                     lambda: fit_files_bench(dev, log, {"f32": round(value, 3), "bf16": (sec.get("bf16") or {}).get("value")}))
             out["secondary"] = sec
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_base:
             out["cpu_baseline"] = cpu_baseline()
             out["cpu_baseline"]["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
-    if world > 1 and not args.no_secondary and args.dtype == "f32":
+    if world > 1 and secondary:
         # configs[4] over all ranks, AFTER the headline has been measured.  The exchange uses RCCL point-to-point calls the training step
         # does not: a watchdog makes sure the headline line is printed even if this part should not come back
         import threading

@@ -5,7 +5,7 @@ TAG=${1:-r01_x}
 DT=${2:-f32}
 R=$PWD; OUT=$R/gpurun_out/prof_$TAG; rm -rf $OUT; mkdir -p $OUT
 python -m unet_amd.build --hash > $OUT/code_hash.txt
-python bench.py --dtype $DT > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+python bench.py --full --dtype $DT > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 tail -1 $OUT/bench.json | cut -c1-200
 export TMPDIR=/tmp; cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --dtype $DT > $OUT/stats.log 2>&1 || { echo "stats pass failed"; exit 1; }

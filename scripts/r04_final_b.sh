@@ -1,7 +1,7 @@
 #!/bin/bash
 # end-of-round evidence, part B: the default bench line on the final code (pmc_traffic.json of part A committed) and the N > 1 rehearsal
 O=gpurun_out
-python bench.py > $O/r04_m_bench.json 2> $O/r04_m_bench.err || { echo bench failed; tail -5 $O/r04_m_bench.err; exit 1; }
+python bench.py --full > $O/r04_m_bench.json 2> $O/r04_m_bench.err || { echo bench failed; tail -5 $O/r04_m_bench.err; exit 1; }
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r04_m_bench.json").read().strip().splitlines()[-1]); s=d.get("secondary",{})
@@ -12,7 +12,7 @@ for k,v in s.items():
     elif isinstance(v,dict): print(k, {kk:(vv.get("value") if isinstance(vv,dict) else vv) for kk,vv in v.items()})
 print(d.get("cpu_baseline"))
 PY
-UNET_DIST_BACKEND=gloo UNET_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --gpus 6 --batch 2 --steps 3 --warmup 2 --no-cpu-baseline > $O/r04_m_rehearsal6.json 2> $O/r04_m_rehearsal6.err; echo "rehearsal rc=$?"
+UNET_DIST_BACKEND=gloo UNET_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --gpus 6 --batch 2 --steps 3 --warmup 2 --full --no-cpu-baseline > $O/r04_m_rehearsal6.json 2> $O/r04_m_rehearsal6.err; echo "rehearsal rc=$?"
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r04_m_rehearsal6.json').read().strip().splitlines()[-1])

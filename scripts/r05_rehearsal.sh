@@ -1,7 +1,7 @@
 #!/bin/bash
 # the N > 1 rehearsal alone: six gloo ranks on the one GPU of the box
 O=gpurun_out
-UNET_DIST_BACKEND=gloo UNET_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --gpus 6 --batch 2 --steps 3 --warmup 2 --no-cpu-baseline > $O/r05_zz_rehearsal6.json 2> $O/r05_zz_rehearsal6.err; echo "rehearsal rc=$?"
+UNET_DIST_BACKEND=gloo UNET_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --gpus 6 --batch 2 --steps 3 --warmup 2 --full --no-cpu-baseline > $O/r05_zz_rehearsal6.json 2> $O/r05_zz_rehearsal6.err; echo "rehearsal rc=$?"
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r05_zz_rehearsal6.json').read().strip().splitlines()[-1])
