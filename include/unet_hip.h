@@ -376,6 +376,11 @@ int unet_adam_step_dev(float* p, const float* g, float* m, float* v, const uint8
 int unet_mosaic_accumulate(const float* probs_nchw, int C, int th, int tw, float* mosaic /*[C,MH,MW]*/,
                            int32_t* count /*[MH,MW]*/, int MH, int MW, int y0, int x0, void* stream);
 int unet_mosaic_finalize(float* mosaic, const int32_t* count, int C, int MH, int MW, uint8_t* argmax, void* stream);
+/* Gaussian-blended form of unet_mosaic_accumulate (the slab add of an N-rank merge): probs [C, th, tw] is added as fl(w * p) with
+ * w = fl(wy[ty] * wx[tx]) (fp32 profile tables of th / tw entries on the device; a slab of the top th rows of a window passes the first
+ * th entries of its vertical profile), w is added to wsum [MH, MW] and the hit counter is incremented.  C <= 64. */
+int unet_mosaic_accumulate_weighted(const float* probs_nchw, int C, int th, int tw, const float* wy, const float* wx, float* mosaic,
+                                    int32_t* count, float* wsum, int MH, int MW, int y0, int x0, void* stream);
 
 /* --------------------------------------- sliding-window predict over a raster --
  * BASELINE.json configs[4]: the raster stays in HBM as the integers it was read as; windows are cut, scaled and merged on the device.
@@ -410,6 +415,15 @@ int unet_mosaic_accumulate_windows(const float* z, int z_cs, int z_co, int C, in
  * fill_host != NULL: pixels without a hit become *fill_host (regression nodata -9999, predict.py:312-315) */
 int unet_mosaic_finalize_rows(float* mosaic, const int32_t* count, int C, int MH, int MW, int row0, int nrows, uint8_t* argmax,
                               const float* fill_host, void* stream);
+/* Gaussian blending (predict.py blend="gaussian"): unet_mosaic_accumulate_windows where window k adds fl(w * p) for each value p it
+ * adds there, w = fl(wy[Y - y0_k] * wx[X - x0_k]) from fp32 profile tables wy [th], wx [tw] on the device, and w is added to wsum
+ * [MH, MW] (fp32, zero-initialised by the caller) in the same window order; the hit counter still counts windows. */
+int unet_mosaic_accumulate_windows_weighted(const float* z, int z_cs, int z_co, int C, int th, int tw, const int32_t* windows, int n,
+                                            int origin_y, int origin_x, int mode, float* mosaic, int32_t* count, int MH, int MW, int row_lo,
+                                            int row_hi, const float* wy, const float* wx, float* wsum, void* stream);
+/* unet_mosaic_finalize_rows with the weight sum as divisor: mosaic /= wsum where count > 0 (IEEE fp32 division), fill / argmax as there */
+int unet_mosaic_finalize_rows_weighted(float* mosaic, const int32_t* count, const float* wsum, int C, int MH, int MW, int row0, int nrows,
+                                       uint8_t* argmax, const float* fill_host, void* stream);
 
 /* Test-time augmentation (TTA).  A D4 code g names one of the 8 symmetries of the square, by its action on the last two axes
  * [..., H, W] of a tensor: 0 x, 1 flip(x, [-1]), 2 flip(x, [-2]), 3 flip(x, [-2, -1]), 4 x^T, 5 rot90(x, 1, (-2, -1)),

@@ -72,11 +72,14 @@ aug_pipe = None
 # test-time augmentation of Predict: None | "flips" (4 passes, any tile shape) | "d4" (8 passes, square tiles) | a tuple of D4 codes
 # (unet_amd/tta.py); every tile's probabilities become the mean over the flipped / rotated passes, mapped back
 TTA = None
+# how the windows of a merged prediction (merge = True) combine: "mean" (the reference's unweighted mean) | "gaussian" (each window
+# weighted with a centre-peaked Gaussian importance map, sigma = tile size / 8: the seams where windows end fade; not with large_file)
+BLEND = "mean"
 
 
 def main():
     global large_file, specific_class, all_classes, transforms, VALID_SCENES, self_attention, monitor, loss_func, LR_FINDER
-    global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA
+    global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND
     t0 = time.time()
     if enable_extra_parameters:          # params_and_main.py:129-145
         import warnings
@@ -86,7 +89,7 @@ def main():
         ENCODER_FACTOR, LR_FINDER, VALID_SCENES, loss_func, monitor = 10, None, ["vali"], None, None
         all_classes, specific_class, enable_regression, large_file, max_empty = False, None, False, False, 0.9
         ARCHITECTURE, self_attention = xresnet34, False
-        TTA = None
+        TTA, BLEND = None, "mean"
     if Create_tiles:
         from create_tiles_unet import split_raster
         split_raster(path_to_raster=image_path, path_to_mask=mask_path, base_dir=base_dir, patch_size=patch_size,
@@ -98,8 +101,9 @@ def main():
                    VALID_SCENES, CODES, transforms, split_idx, export_model_summary, aug_pipe, n_transform_imgs, info, class_zero)
     if Predict:
         from predict import save_predictions
+        extra = {} if BLEND == "mean" else {"blend": BLEND}
         save_predictions(predict_model, predict_path, regression, merge, all_classes, specific_class, large_file, AOI, year,
-                         validation_vision, class_zero, tta=TTA)
+                         validation_vision, class_zero, tta=TTA, **extra)
     print(f"Operation completed in {(time.time() - t0) / 60:.2f} minutes.")
 
 

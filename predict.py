@@ -22,6 +22,13 @@ points, merged and per tile.  Every batch runs k forwards of the same geometry o
 outputs are mapped back and averaged per window on the device in code order (``unet_tta_accumulate``), and that mean takes the place of the
 window's softmax probabilities in the merge, the slabs, the int8 ``large_file`` merge and the per-tile outputs.  The hit counter still counts
 windows.
+
+Also beyond the reference: ``blend=`` ("mean" | "gaussian") of both entry points' merged outputs.  "mean" is the reference's merge above.
+"gaussian" weights every window's contribution to a pixel with a centre-peaked importance map (the product of two 1-D Gaussians, sigma =
+window side / 8, ``unet_amd/mosaic.py``), as nnU-Net and MONAI's sliding-window inference do, so that pixels near a window's edge -- predicted
+with half their context -- count less than the same pixels seen from the middle of the next window and the seams fade.  The weighted sum
+and the weight sum are accumulated on the device in the same order as the mean (``unet_mosaic_accumulate_windows_weighted``, the weighted
+slab add and finalisation), so N ranks equal 1 rank bit for bit here too.  Refused (ValueError) for ``large_file`` and per-tile outputs.
 """
 from __future__ import annotations
 
@@ -39,7 +46,7 @@ import torch
 
 from unet_amd import ops
 from unet_amd.learner import load_learner, open_tile
-from unet_amd.mosaic import MergePlan, keep_windows, merge_order, sliding_windows
+from unet_amd.mosaic import MergePlan, blend_profile, check_blend, keep_windows, merge_order, sliding_windows
 from unet_amd.tiffio import read_tiff, tiff_info, write_tiff
 from unet_amd.tta import parse as tta_codes
 
@@ -106,7 +113,8 @@ class _Merge:
     """Runs one rank's share of a merged prediction: forward of its placements in batches, accumulation into its strip of the
     mosaic, slab exchange with the neighbours, finalisation, gather of the requested output on rank 0."""
 
-    def __init__(self, model, places: np.ndarray, MH: int, MW: int, regression: bool, int8_merge: bool, rank: int, world: int, batch: int):
+    def __init__(self, model, places: np.ndarray, MH: int, MW: int, regression: bool, int8_merge: bool, rank: int, world: int, batch: int,
+                 blend: str = "mean"):
         self.model, self.dev = model, model._device
         self.C = model.n_out
         self.raw, self.int8 = bool(regression), bool(int8_merge)
@@ -120,6 +128,11 @@ class _Merge:
         else:
             self.mosaic = torch.zeros((self.C, max(rows, 1), MW), dtype=torch.float32, device=self.dev)
             self.count = torch.zeros((max(rows, 1), MW), dtype=torch.int32, device=self.dev)
+        # Gaussian blending: the weight sum of every strip pixel (the divisor in place of the hit counter) and the device profile tables,
+        # one per window side length, uploaded once per call
+        self.blend = check_blend(blend, self.int8)
+        self.wsum = torch.zeros((max(rows, 1), MW), dtype=torch.float32, device=self.dev) if self.blend == "gaussian" else None
+        self._profiles = {}
         self.acc_table = ops.window_table(self.plan.places[:, :2].tolist(), self.dev)       # (y0, x0) in mosaic coordinates
         self.my_slabs = self.plan.slabs(rank)
         self._slab_off, off = {}, 0
@@ -127,6 +140,12 @@ class _Merge:
             self._slab_off[i] = (off, r)
             off += self.C * r * int(self.plan.places[i, 3])
         self.sendbuf = torch.empty(off, dtype=torch.float32, device=self.dev) if off else None
+
+    def _profile(self, n: int) -> torch.Tensor:
+        t = self._profiles.get(n)
+        if t is None:
+            t = self._profiles[n] = torch.from_numpy(blend_profile(n)).to(self.dev)
+        return t
 
     # -- int8 "large_file" accumulation of one window's probabilities [C, rows, w] at strip row y (may be clipped), column x
     def _add_int8(self, probs: torch.Tensor, y: int, x: int):
@@ -152,8 +171,11 @@ class _Merge:
                 for j in range(n):
                     y0, x0 = self.plan.places[first + j, :2]
                     self._add_int8(probs[j], int(y0) - self.lo, int(x0))
-            else:
+            elif self.wsum is None:
                 ops.mosaic_accumulate_windows(z, self.acc_table, first, n, (self.lo, 0), self.mosaic, self.count, 0, rows, raw=raw)
+            else:
+                ops.mosaic_accumulate_windows_weighted(z, self.acc_table, first, n, (self.lo, 0), self.mosaic, self.count, self.wsum,
+                                                       self._profile(z.H), self._profile(z.W), 0, rows, raw=raw)
         for j in range(n):          # rows that belong to the strip above: per-window slabs for rank - 1
             ent = self._slab_off.get(first + j)
             if ent is None:
@@ -168,7 +190,8 @@ class _Merge:
                 ops.softmax_argmax(zs, out, None)
 
     def exchange(self):
-        """slabs up to rank - 1, slabs of rank + 1 added on top of the own windows (in placement order)"""
+        """slabs up to rank - 1, slabs of rank + 1 added on top of the own windows (in placement order); a blended merge weights a slab
+        here, on the receiving side, with rows [0, rr) of the sender window's vertical profile"""
         if self.world == 1 or self.plan.active == 1:
             return
         r, act = self.rank, self.plan.active
@@ -180,13 +203,15 @@ class _Merge:
             return
         off = 0
         for i, rr in self.plan.slabs(r + 1):
-            y0, x0, _, w = (int(v) for v in self.plan.places[i])
+            y0, x0, h, w = (int(v) for v in self.plan.places[i])
             slab = got[off:off + self.C * rr * w].view(self.C, rr, w)
             off += self.C * rr * w
             if self.int8:
                 self._add_int8(slab, y0 - self.lo, x0)
-            else:
+            elif self.wsum is None:
                 ops.mosaic_accumulate(slab, self.mosaic, self.count, y0 - self.lo, x0)
+            else:
+                ops.mosaic_accumulate_weighted(slab, self._profile(h), self._profile(w), self.mosaic, self.count, self.wsum, y0 - self.lo, x0)
 
     def finish(self, want):
         """want: "argmax" | "all" | int class index.  Returns (on rank 0) the full-size numpy array, None elsewhere."""
@@ -199,8 +224,10 @@ class _Merge:
             part = torch.from_numpy(np.ascontiguousarray(part))
         else:
             am = torch.empty((max(rows, 1), MW), dtype=torch.uint8, device=self.dev) if want == "argmax" else None
-            if rows > 0:
+            if rows > 0 and self.wsum is None:
                 ops.mosaic_finalize_rows(self.mosaic, self.count, 0, rows, am, fill=-9999.0 if self.raw else None)
+            elif rows > 0:
+                ops.mosaic_finalize_rows_weighted(self.mosaic, self.count, self.wsum, 0, rows, am, fill=-9999.0 if self.raw else None)
             part = am[:rows] if want == "argmax" else (self.mosaic[:, :rows] if want == "all" else self.mosaic[want, :rows])
         return self._gather_rows(part, want == "all")
 
@@ -253,11 +280,12 @@ class _TTAAccumulator:
 
 
 def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch, make_input: Callable, want, timing: Optional[dict] = None,
-               tta: Optional[Tuple[int, ...]] = None):
+               tta: Optional[Tuple[int, ...]] = None, blend: str = "mean"):
     """make_input(first, n, n_pad) -> ops.WindowBatch of placements [first, first + n) padded to n_pad windows (so that every
     forward runs on ONE batch geometry and no second set of activation buffers is allocated).  tta: parsed codes -- every batch runs
-    len(tta) forwards of that same geometry and the averaged probabilities take the place of the softmax in the merge"""
-    mg = _Merge(model, places, MH, MW, regression, int8_merge, rank, world, batch)
+    len(tta) forwards of that same geometry and the averaged probabilities take the place of the softmax in the merge.  blend: "mean" |
+    "gaussian" (unet_amd/mosaic.py)"""
+    mg = _Merge(model, places, MH, MW, regression, int8_merge, rank, world, batch, blend)
     acc = None if tta is None else _TTAAccumulator(model, tta, bool(regression))
     t0 = time.perf_counter()
     done = 0
@@ -330,7 +358,7 @@ def _raster_plan(wins: np.ndarray, size: int, H: int, W: int, batch_size: int):
 def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_empty: float = 0.9, dtype: str = "int8", nodata=None,
                    regression: bool = False, all_classes: bool = False, specific_class: Optional[int] = None, large_file: bool = False,
                    batch_size: int = 16, out_path=None, class_zero: bool = False, timing: Optional[dict] = None,
-                   batch_invariant: bool = False, tta=None):
+                   batch_invariant: bool = False, tta=None, blend: str = "mean"):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -348,9 +376,13 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
              counters, integer floor division -- same numbers as save_predictions(merge=True, large_file=True)
     tta      None | "flips" | "d4" | a tuple of D4 codes (unet_amd/tta.py): test-time augmentation -- every window's probabilities (regression:
              values) are the mean of g^-1(f(g(window))) over the set, computed before the merge; the hit counter still counts windows
+    blend    "mean" (the reference's merge: unweighted mean of the windows that cover a pixel) | "gaussian": every window's contribution
+             is weighted with a centre-peaked Gaussian importance map (sigma = window side / 8, unet_amd/mosaic.py blend_profile) and the
+             pixel is the weighted mean; not with large_file (ValueError)
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
+    check_blend(blend, large_file)
     model = getattr(model, "model", model)
     codes = tta_codes(tta, [(size, size)])
     rank, local_rank, world = _dist_ctx()
@@ -392,7 +424,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     want = _want(regression, all_classes, specific_class)
     with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
         out = _run_merge(model, places, MH, MW, regression, bool(large_file and not regression), rank, world, batch_size, make_input, want, timing,
-                         codes)
+                         codes, blend)
     if rank == 0 and out_path is not None:
         ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
         store_tif(out_path, out, ogt, tags, -9999 if regression else None, class_zero)
@@ -518,8 +550,11 @@ def _prefetcher(tiles, batches, sizes, device):
 
 def save_predictions(predict_model, predict_path, regression, merge=False, all_classes=False, specific_class=None, large_file=False,
                      AOI=None, year=None, validation_vision=True, class_zero=False, batch_size=16, timing: Optional[dict] = None,
-                     batch_invariant: bool = False, tta=None):
-    """tta: None | "flips" | "d4" | a tuple of D4 codes (see predict_raster and unet_amd/tta.py), merged and per-tile outputs alike"""
+                     batch_invariant: bool = False, tta=None, blend: str = "mean"):
+    """tta: None | "flips" | "d4" | a tuple of D4 codes (see predict_raster and unet_amd/tta.py), merged and per-tile outputs alike.
+    blend: "mean" | "gaussian" (see predict_raster): how the windows of a merged prediction combine; only with merge=True (per-tile
+    outputs have no overlap) and not with large_file (ValueError before the model is loaded)"""
+    check_blend(blend, large_file, merge)
     rank, local_rank, world = _dist_ctx()
     dist = _dist()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
@@ -584,7 +619,8 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
         want = _want(regression, all_classes, specific_class)
         try:
             with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):          # (see predict_raster)
-                out = _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch_size, make_input, want, timing, codes)
+                out = _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch_size, make_input, want, timing, codes,
+                                 blend)
         finally:
             feed.close()
             if hasattr(pf, "close"):

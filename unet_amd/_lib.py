@@ -185,6 +185,9 @@ _sig = {
     "unet_window_gather_oriented": (i, [vp, i, i, ll, ll, i, vp, i, i, i, i, vp, i, i, i, i, vp]),
     "unet_nchw_to_nhwc_oriented": (i, [vp, vp, i, i, i, i, i, i, i, i, vp]),
     "unet_tta_accumulate": (i, [vp, i, i, i, i, i, i, i, i, i, vp, i, i, vp, vp, vp]),
+    "unet_mosaic_accumulate_weighted": (i, [vp, i, i, i, vp, vp, vp, vp, vp, i, i, i, i, vp]),
+    "unet_mosaic_accumulate_windows_weighted": (i, [vp, i, i, i, i, i, vp, i, i, i, i, vp, vp, i, i, i, i, vp, vp, vp, vp]),
+    "unet_mosaic_finalize_rows_weighted": (i, [vp, vp, vp, i, i, i, i, i, vp, c_float_p, vp]),
 }
 # bf16-storage twins: same argument lists (every tensor is a void pointer on this side)
 for _n in ("bn_stats", "affine_act", "bn_bwd_reduce", "bn_bwd_apply", "maxpool3x3s2", "maxpool3x3s2_bwd", "avgpool2_ceil",

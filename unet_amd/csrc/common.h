@@ -62,6 +62,14 @@ static inline int ew_grid(long long work_items, int block) {
     return (int)g;
 }
 
+// fl(a * b), rounded on its own: never contracted into an FMA with the add that consumes it.  (__fmul_rn / __fadd_rn are a plain `*` /
+// `+` in the HIP headers unless OCML_BASIC_ROUNDED_OPERATIONS is defined, and hipcc contracts `__fadd_rn(s, __fmul_rn(a, b))` into one
+// fma.  A multiply compiled under contract(off) carries no contract flag, so no add can absorb it.)
+__device__ __forceinline__ float fmul_unfused(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 }  // namespace unet
 
 namespace unetconv {

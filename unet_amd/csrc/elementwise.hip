@@ -33,6 +33,7 @@ namespace {
 
 using unet::cdiv;
 using unet::ew_grid;
+using unet::fmul_unfused;
 using unet::roundup;
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -1397,14 +1398,26 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 }
 
 // -------------------------------------------------------------- mosaic
+// WEIGHTED (Gaussian blending): probs[c] is added as fl(w * probs[c]) with w = fl(wy[ty] * wx[tx]), and w is added to wsum [MH, MW]
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void mosaic_acc_kernel(const float* __restrict__ probs, int C, int th, int tw, float* __restrict__ mosaic,
-                                                         int32_t* __restrict__ count, int MH, int MW, int y0, int x0) {
+                                                         int32_t* __restrict__ count, int MH, int MW, int y0, int x0, const float* __restrict__ wy,
+                                                         const float* __restrict__ wx, float* __restrict__ wsum) {
     const long long total = (long long)th * tw;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int ty = (int)(i / tw), tx = (int)(i % tw);
         const int my = y0 + ty, mx = x0 + tx;
         if (my < 0 || my >= MH || mx < 0 || mx >= MW) continue;
-        for (int c = 0; c < C; ++c) mosaic[((size_t)c * MH + my) * MW + mx] += probs[((size_t)c * th + ty) * tw + tx];
+        if constexpr (WEIGHTED) {
+            const float w = fmul_unfused(wy[ty], wx[tx]);
+            for (int c = 0; c < C; ++c) {
+                float* q = mosaic + ((size_t)c * MH + my) * MW + mx;
+                *q = __fadd_rn(*q, fmul_unfused(w, probs[((size_t)c * th + ty) * tw + tx]));
+            }
+            wsum[(size_t)my * MW + mx] = __fadd_rn(wsum[(size_t)my * MW + mx], w);
+        } else {
+            for (int c = 0; c < C; ++c) mosaic[((size_t)c * MH + my) * MW + mx] += probs[((size_t)c * th + ty) * tw + tx];
+        }
         count[(size_t)my * MW + mx] += 1;
     }
 }
@@ -2043,8 +2056,18 @@ extern "C" int unet_adam_step(float* p, const float* g, float* m, float* v, cons
 extern "C" int unet_mosaic_accumulate(const float* probs_nchw, int C, int th, int tw, float* mosaic, int32_t* count, int MH, int MW, int y0,
                                       int x0, void* stream) {
     UNET_CHECK_ARG(probs_nchw && mosaic && count && C > 0 && th > 0 && tw > 0 && MH > 0 && MW > 0, "mosaic_accumulate: bad args");
-    hipLaunchKernelGGL(mosaic_acc_kernel, dim3(ew_grid((long long)th * tw, 256)), dim3(256), 0, ST, probs_nchw, C, th, tw, mosaic, count, MH, MW,
-                       y0, x0);
+    hipLaunchKernelGGL(mosaic_acc_kernel<false>, dim3(ew_grid((long long)th * tw, 256)), dim3(256), 0, ST, probs_nchw, C, th, tw, mosaic, count, MH,
+                       MW, y0, x0, nullptr, nullptr, nullptr);
+    UNET_CHECK_LAUNCH();
+    return UNET_OK;
+}
+
+extern "C" int unet_mosaic_accumulate_weighted(const float* probs_nchw, int C, int th, int tw, const float* wy, const float* wx, float* mosaic,
+                                               int32_t* count, float* wsum, int MH, int MW, int y0, int x0, void* stream) {
+    UNET_CHECK_ARG(probs_nchw && wy && wx && mosaic && count && wsum && C > 0 && C <= CE_MAXC && th > 0 && tw > 0 && MH > 0 && MW > 0,
+                   "mosaic_accumulate_weighted: bad args");
+    hipLaunchKernelGGL(mosaic_acc_kernel<true>, dim3(ew_grid((long long)th * tw, 256)), dim3(256), 0, ST, probs_nchw, C, th, tw, mosaic, count, MH,
+                       MW, y0, x0, wy, wx, wsum);
     UNET_CHECK_LAUNCH();
     return UNET_OK;
 }

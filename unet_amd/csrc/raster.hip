@@ -246,10 +246,14 @@ constexpr int MAXC = 64;      // class count bound shared with the loss kernels 
 // mode 0: softmax over the C logits (classification)   1: raw values (regression, predict.py:195-197)
 // Thread (j, y, x) owns mosaic pixel (Y, X) of window j only when no earlier window of this launch covers it; it then adds the
 // contributions of windows j, j+1, ... that cover (Y, X) in that order: every mosaic pixel is updated by one thread, in window order.
+// WEIGHTED (Gaussian blending): the contribution p of window k is fl(w * p) with w = fl(wy[Y - y0_k] * wx[X - x0_k]) (fp32 profile
+// tables of th / tw entries), and w is added to wsum [MH, MW] in the same order; the hit counter still counts windows.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void mosaic_acc_windows_kernel(const float* __restrict__ z, int z_cs, int z_co, int C, int th, int tw,
                                                                  const int* __restrict__ win, int n, int oy, int ox, int mode,
                                                                  float* __restrict__ mosaic, int32_t* __restrict__ count, int MH, int MW,
-                                                                 int row_lo, int row_hi) {
+                                                                 int row_lo, int row_hi, const float* __restrict__ wy,
+                                                                 const float* __restrict__ wx, float* __restrict__ wsum) {
     __shared__ int sy[MAXWIN], sx[MAXWIN];
     if (threadIdx.x < n) {
         sy[threadIdx.x] = win[4 * threadIdx.x] - oy;
@@ -268,9 +272,16 @@ __global__ __launch_bounds__(256) void mosaic_acc_windows_kernel(const float* __
         if (!first) continue;
         const size_t m = (size_t)Y * MW + X;
         int hits = 0;
+        float ws = 0.f;
+        if constexpr (WEIGHTED) ws = wsum[m];
         for (int k = j; k < n; ++k) {
             if (!(Y >= sy[k] && Y < sy[k] + th && X >= sx[k] && X < sx[k] + tw)) continue;
             const float* zp = z + ((size_t)k * per + (size_t)(Y - sy[k]) * tw + (X - sx[k])) * z_cs + z_co;
+            float w = 1.f;
+            if constexpr (WEIGHTED) {
+                w = fmul_unfused(wy[Y - sy[k]], wx[X - sx[k]]);
+                ws = __fadd_rn(ws, w);
+            }
             if (mode == 0) {        // exactly the arithmetic of softmax_argmax_kernel (elementwise.hip): a tile's probabilities are the same numbers
                 float mx = zp[0];
                 for (int c = 1; c < C; ++c) mx = fmaxf(mx, zp[c]);
@@ -278,41 +289,52 @@ __global__ __launch_bounds__(256) void mosaic_acc_windows_kernel(const float* __
                 for (int c = 0; c < C; ++c) s += expf(zp[c] - mx);
                 for (int c = 0; c < C; ++c) {
                     float* q = mosaic + (size_t)c * plane + m;
-                    *q = __fadd_rn(*q, expf(zp[c] - mx) / s);
+                    float v = expf(zp[c] - mx) / s;
+                    if constexpr (WEIGHTED) v = fmul_unfused(w, v);
+                    *q = __fadd_rn(*q, v);
                 }
             } else {
                 for (int c = 0; c < C; ++c) {
                     float* q = mosaic + (size_t)c * plane + m;
-                    *q = __fadd_rn(*q, zp[c]);
+                    float v = zp[c];
+                    if constexpr (WEIGHTED) v = fmul_unfused(w, v);
+                    *q = __fadd_rn(*q, v);
                 }
             }
             ++hits;
         }
         count[m] += hits;
+        if constexpr (WEIGHTED) wsum[m] = ws;
     }
 }
 
 // rows [row0, row0 + nrows) of a [C][MH][MW] mosaic: mean over the hits, argmax (first maximum, as numpy), optional fill where nothing
-// was placed (regression: predict.py:312-315)
+// was placed (regression: predict.py:312-315).  WEIGHTED: the divisor is the weight sum wsum [MH, MW] (where the count is positive).
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void mosaic_fin_rows_kernel(float* __restrict__ mosaic, const int32_t* __restrict__ count, int C, int MH,
                                                               int MW, int row0, int nrows, uint8_t* __restrict__ amax, int has_fill,
-                                                              float fill) {
+                                                              float fill, const float* __restrict__ wsum) {
     const long long total = (long long)nrows * MW, plane = (long long)MH * MW;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const size_t m = (size_t)row0 * MW + i;
         const int cnt = count[m];
+        float den = 0.f;
+        if constexpr (WEIGHTED) den = wsum[m];
         float best = -INFINITY;
         int bi = 0;
         for (int c = 0; c < C; ++c) {
             float v = mosaic[(size_t)c * plane + m];
-            if (cnt > 0) { v = v / (float)cnt; mosaic[(size_t)c * plane + m] = v; }
+            if (cnt > 0) {
+                if constexpr (WEIGHTED) v = v / den;
+                else v = v / (float)cnt;
+                mosaic[(size_t)c * plane + m] = v;
+            }
             else if (has_fill) { v = fill; mosaic[(size_t)c * plane + m] = v; }
             if (v > best) { best = v; bi = c; }
         }
         if (amax) amax[i] = (uint8_t)bi;
     }
 }
-
 
 // ---- training feed (reference train.py:345 -> data.py:18-28 open_npy, utils.py:239-295 the batch transform, IntToFloatTensor) ----
 // A batch arrives as the INTEGERS of its tile files (pinned staging -> one asynchronous copy); value scaling, the int64 widening of the
@@ -499,29 +521,65 @@ extern "C" int unet_tta_accumulate(const float* z, int z_cs, int z_co, int n, in
     return UNET_OK;
 }
 
+namespace {
+
+template <bool WEIGHTED>
+int mosaic_accumulate_windows_impl(const float* z, int z_cs, int z_co, int C, int th, int tw, const int32_t* windows, int n, int origin_y,
+                                   int origin_x, int mode, float* mosaic, int32_t* count, int MH, int MW, int row_lo, int row_hi,
+                                   const float* wy, const float* wx, float* wsum, void* stream) {
+    for (int b = 0; b < n; b += MAXWIN) {      // launches are stream ordered: later windows land on top of earlier ones
+        const int nb = n - b < MAXWIN ? n - b : MAXWIN;
+        hipLaunchKernelGGL(mosaic_acc_windows_kernel<WEIGHTED>, dim3(ew_grid((long long)nb * th * tw, 256)), dim3(256), 0, ST,
+                           z + (size_t)b * th * tw * z_cs, z_cs, z_co, C, th, tw, windows + 4 * b, nb, origin_y, origin_x, mode, mosaic, count,
+                           MH, MW, row_lo, row_hi, wy, wx, wsum);
+        UNET_CHECK_LAUNCH();
+    }
+    return UNET_OK;
+}
+
+template <bool WEIGHTED>
+int mosaic_finalize_rows_impl(float* mosaic, const int32_t* count, const float* wsum, int C, int MH, int MW, int row0, int nrows,
+                              uint8_t* argmax, const float* fill_host, void* stream) {
+    hipLaunchKernelGGL(mosaic_fin_rows_kernel<WEIGHTED>, dim3(ew_grid((long long)nrows * MW, 256)), dim3(256), 0, ST, mosaic, count, C, MH, MW,
+                       row0, nrows, argmax, fill_host ? 1 : 0, fill_host ? *fill_host : 0.f, wsum);
+    UNET_CHECK_LAUNCH();
+    return UNET_OK;
+}
+
+}  // namespace
+
 extern "C" int unet_mosaic_accumulate_windows(const float* z, int z_cs, int z_co, int C, int th, int tw, const int32_t* windows, int n,
                                               int origin_y, int origin_x, int mode, float* mosaic, int32_t* count, int MH, int MW, int row_lo,
                                               int row_hi, void* stream) {
     UNET_CHECK_ARG(z && windows && mosaic && count && C > 0 && C <= MAXC && th > 0 && tw > 0 && MH > 0 && MW > 0 && n > 0,
                    "mosaic_accumulate_windows: bad args");
     UNET_CHECK_ARG(z_co >= 0 && z_co + C <= z_cs && (mode == 0 || mode == 1), "mosaic_accumulate_windows: bad slice / mode");
-    for (int b = 0; b < n; b += MAXWIN) {      // launches are stream ordered: later windows land on top of earlier ones
-        const int nb = n - b < MAXWIN ? n - b : MAXWIN;
-        hipLaunchKernelGGL(mosaic_acc_windows_kernel, dim3(ew_grid((long long)nb * th * tw, 256)), dim3(256), 0, ST,
-                           z + (size_t)b * th * tw * z_cs, z_cs, z_co, C, th, tw, windows + 4 * b, nb, origin_y, origin_x, mode, mosaic, count,
-                           MH, MW, row_lo, row_hi);
-        UNET_CHECK_LAUNCH();
-    }
-    return UNET_OK;
+    return mosaic_accumulate_windows_impl<false>(z, z_cs, z_co, C, th, tw, windows, n, origin_y, origin_x, mode, mosaic, count, MH, MW, row_lo,
+                                                 row_hi, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int unet_mosaic_accumulate_windows_weighted(const float* z, int z_cs, int z_co, int C, int th, int tw, const int32_t* windows,
+                                                       int n, int origin_y, int origin_x, int mode, float* mosaic, int32_t* count, int MH,
+                                                       int MW, int row_lo, int row_hi, const float* wy, const float* wx, float* wsum,
+                                                       void* stream) {
+    UNET_CHECK_ARG(z && windows && mosaic && count && wy && wx && wsum && C > 0 && C <= MAXC && th > 0 && tw > 0 && MH > 0 && MW > 0 && n > 0,
+                   "mosaic_accumulate_windows_weighted: bad args");
+    UNET_CHECK_ARG(z_co >= 0 && z_co + C <= z_cs && (mode == 0 || mode == 1), "mosaic_accumulate_windows_weighted: bad slice / mode");
+    return mosaic_accumulate_windows_impl<true>(z, z_cs, z_co, C, th, tw, windows, n, origin_y, origin_x, mode, mosaic, count, MH, MW, row_lo,
+                                                row_hi, wy, wx, wsum, stream);
 }
 
 extern "C" int unet_mosaic_finalize_rows(float* mosaic, const int32_t* count, int C, int MH, int MW, int row0, int nrows, uint8_t* argmax,
                                          const float* fill_host, void* stream) {
     UNET_CHECK_ARG(mosaic && count && C > 0 && MH > 0 && MW > 0 && row0 >= 0 && nrows > 0 && row0 + nrows <= MH, "mosaic_finalize_rows: bad args");
-    hipLaunchKernelGGL(mosaic_fin_rows_kernel, dim3(ew_grid((long long)nrows * MW, 256)), dim3(256), 0, ST, mosaic, count, C, MH, MW, row0, nrows,
-                       argmax, fill_host ? 1 : 0, fill_host ? *fill_host : 0.f);
-    UNET_CHECK_LAUNCH();
-    return UNET_OK;
+    return mosaic_finalize_rows_impl<false>(mosaic, count, nullptr, C, MH, MW, row0, nrows, argmax, fill_host, stream);
+}
+
+extern "C" int unet_mosaic_finalize_rows_weighted(float* mosaic, const int32_t* count, const float* wsum, int C, int MH, int MW, int row0,
+                                                  int nrows, uint8_t* argmax, const float* fill_host, void* stream) {
+    UNET_CHECK_ARG(mosaic && count && wsum && C > 0 && C <= MAXC && MH > 0 && MW > 0 && row0 >= 0 && nrows > 0 && row0 + nrows <= MH,
+                   "mosaic_finalize_rows_weighted: bad args");
+    return mosaic_finalize_rows_impl<true>(mosaic, count, wsum, C, MH, MW, row0, nrows, argmax, fill_host, stream);
 }
 
 extern "C" int unet_tiles_stage(const void* src, int rtype, int n, int bands, int H, int W, int div255_twice, unsigned long long hflip,

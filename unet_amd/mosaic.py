@@ -14,12 +14,44 @@ defined order whatever the number of ranks:
   so the N-rank result equals the 1-rank result bit for bit, and the only exchange is the overlap rows (cfg5: <= 300 MB per boundary
   instead of an 8 GB all-reduce of whole mosaics);
 * every rank finalises its strip (divide, argmax) and only the requested band(s) travel to rank 0.
+
+Gaussian blending (``blend="gaussian"``, beyond the reference): window k adds fl(w * p) for every value p it would add, with the
+centre-peaked weight w = fl(g_h[Y - y0] * g_w[X - x0]) of ``blend_profile``, and w goes into a per-pixel weight sum that takes the
+place of the hit counter as divisor.  The receiver of a slab applies the weights (rows [0, rows) of the sender window's vertical profile),
+so the slabs and the ordering argument above stay as they are: N ranks still equal 1 rank bit for bit.
 """
 from __future__ import annotations
 
 from typing import List, Tuple
 
 import numpy as np
+
+
+BLENDS = ("mean", "gaussian")
+
+
+def blend_profile(n: int) -> np.ndarray:
+    """float32 [n]: the 1-D Gaussian importance profile of a window side of n pixels, g[t] = exp(-(t - (n-1)/2)^2 / (2 sigma^2)) with
+    sigma = n / 8 (nnU-Net's sliding-window predictor, MONAI's sigma_scale = 0.125), computed in float64, divided by its maximum, rounded
+    to float32.  Its smallest entry is exp(-8 (n-1)^2 / n^2) >= ~3.4e-4: no weight is zero."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"blend profile of {n} pixels")
+    t = np.arange(n, dtype=np.float64)
+    sigma = n / 8.0
+    g = np.exp(-((t - (n - 1) / 2.0) ** 2) / (2.0 * sigma * sigma))
+    return (g / g.max()).astype(np.float32)
+
+
+def check_blend(blend: str, large_file: bool = False, merge: bool = True) -> str:
+    """the blend= argument of predict_raster / save_predictions, validated before anything is uploaded"""
+    if blend not in BLENDS:
+        raise ValueError(f"blend={blend!r}: expected one of {BLENDS}")
+    if blend != "mean" and large_file:
+        raise ValueError(f"blend={blend!r} with large_file=True: the int8 merge divides integers, it has no weighted form")
+    if blend != "mean" and not merge:
+        raise ValueError(f"blend={blend!r} needs merge=True: per-tile predictions have no overlap to blend")
+    return blend
 
 
 def window_offsets(length: int, size: int, step: int) -> List[int]:

@@ -779,6 +779,22 @@ def mosaic_finalize(mosaic: torch.Tensor, count: torch.Tensor, amax: Optional[to
     check(lib.unet_mosaic_finalize(mosaic.data_ptr(), count.data_ptr(), Cc, MH, MW, _p(amax), _stream()), "mosaic_finalize")
 
 
+def _blend_tables(what: str, wy: torch.Tensor, wx: torch.Tensor, th: int, tw: int):
+    assert wy.dtype == torch.float32 and wx.dtype == torch.float32 and wy.is_contiguous() and wx.is_contiguous(), what
+    assert wy.numel() >= th and wx.numel() >= tw, (what, wy.numel(), th, wx.numel(), tw)
+
+
+def mosaic_accumulate_weighted(probs: torch.Tensor, wy: torch.Tensor, wx: torch.Tensor, mosaic: torch.Tensor, count: torch.Tensor,
+                               wsum: torch.Tensor, y0: int, x0: int):
+    """the Gaussian-blended slab add: probs [C, th, tw] added as fl(w * p), w = fl(wy[ty] * wx[tx]); w added to wsum"""
+    Cc, th, tw = probs.shape
+    _, MH, MW = mosaic.shape
+    _blend_tables("mosaic_accumulate_weighted", wy, wx, th, tw)
+    assert wsum.shape == (MH, MW) and wsum.dtype == torch.float32 and count.shape == (MH, MW)
+    check(lib.unet_mosaic_accumulate_weighted(probs.data_ptr(), Cc, th, tw, wy.data_ptr(), wx.data_ptr(), mosaic.data_ptr(), count.data_ptr(),
+                                              wsum.data_ptr(), MH, MW, y0, x0, _stream()), "mosaic_accumulate_weighted")
+
+
 # ------------------------------------------------------------------ sliding-window predict over an integer raster (csrc/raster.hip)
 
 RASTER_TYPES = {torch.uint8: 0, torch.uint16: 1, torch.int16: 2, torch.int32: 3, torch.float32: 4}
@@ -988,3 +1004,29 @@ def mosaic_finalize_rows(mosaic: torch.Tensor, count: torch.Tensor, row0: int, n
     fp = None if fill is None else C.byref(C.c_float(float(fill)))
     check(lib.unet_mosaic_finalize_rows(mosaic.data_ptr(), count.data_ptr(), Cc, MH, MW, row0, nrows, _p(amax),
                                         None if fp is None else C.cast(fp, L.c_float_p), _stream()), "mosaic_finalize_rows")
+
+
+def mosaic_accumulate_windows_weighted(z: TS, table: torch.Tensor, first: int, n: int, origin, mosaic: torch.Tensor, count: torch.Tensor,
+                                       wsum: torch.Tensor, wy: torch.Tensor, wx: torch.Tensor, row_lo: int, row_hi: int, raw: bool = False):
+    """mosaic_accumulate_windows with Gaussian blending: every value is added as fl(w * v), w = fl(wy[ty] * wx[tx]) of the window's
+    profile tables (fp32, z.H / z.W entries), and w is added to wsum [MH, MW]"""
+    _need_f32("mosaic_accumulate_windows_weighted", z)
+    Cc, MH, MW = mosaic.shape
+    assert z.N >= n and Cc == z.C and count.shape == (MH, MW) and count.dtype == torch.int32 and mosaic.dtype == torch.float32
+    assert wsum.shape == (MH, MW) and wsum.dtype == torch.float32
+    _blend_tables("mosaic_accumulate_windows_weighted", wy, wx, z.H, z.W)
+    check(lib.unet_mosaic_accumulate_windows_weighted(z.ptr, z.cs, z.co, z.C, z.H, z.W, table.data_ptr() + 16 * first, n, int(origin[0]),
+                                                      int(origin[1]), int(raw), mosaic.data_ptr(), count.data_ptr(), MH, MW, int(row_lo),
+                                                      int(row_hi), wy.data_ptr(), wx.data_ptr(), wsum.data_ptr(), _stream()),
+          "mosaic_accumulate_windows_weighted")
+
+
+def mosaic_finalize_rows_weighted(mosaic: torch.Tensor, count: torch.Tensor, wsum: torch.Tensor, row0: int, nrows: int,
+                                  amax: Optional[torch.Tensor], fill=None):
+    """mosaic_finalize_rows with the weight sum as divisor (where the hit count is positive)"""
+    Cc, MH, MW = mosaic.shape
+    assert amax is None or (amax.dtype == torch.uint8 and amax.numel() >= nrows * MW)
+    assert wsum.shape == (MH, MW) and wsum.dtype == torch.float32
+    fp = None if fill is None else C.byref(C.c_float(float(fill)))
+    check(lib.unet_mosaic_finalize_rows_weighted(mosaic.data_ptr(), count.data_ptr(), wsum.data_ptr(), Cc, MH, MW, row0, nrows, _p(amax),
+                                                 None if fp is None else C.cast(fp, L.c_float_p), _stream()), "mosaic_finalize_rows_weighted")
