@@ -45,6 +45,7 @@ import numpy as np
 import torch
 
 from unet_amd import ops
+from unet_amd.feed import BatchFeeder, default_workers, torch_samples
 from unet_amd.learner import load_learner, open_tile
 from unet_amd.mosaic import MergePlan, blend_profile, check_blend, keep_windows, merge_order, sliding_windows
 from unet_amd.tiffio import read_tiff, tiff_info, write_tiff
@@ -69,19 +70,6 @@ def _geo(path):
 
 
 LARGE_FILE_SCALE = (128 / 4) - 1        # predict.py:209-214: probabilities stretched to int8 as around(p * 31)
-_SAMPLE_TYPES = (np.uint8, np.uint16, np.int16, np.int32, np.float32)
-
-
-def _as_samples(a: np.ndarray) -> np.ndarray:
-    """sample array the device kernels read as is; anything else goes through int32, which is what data.py:24 does to every tile anyway"""
-    return a if a.dtype.type in _SAMPLE_TYPES else a.astype(np.int32)
-
-
-def _torch_samples(a: np.ndarray) -> torch.Tensor:
-    a = np.ascontiguousarray(_as_samples(a))
-    if a.dtype == np.uint16:        # torch.from_numpy has no uint16 before 2.3; view the bits
-        return torch.from_numpy(a.view(np.int16)).view(torch.uint16)
-    return torch.from_numpy(a)
 
 
 # ----------------------------------------------------------------------------------------------- p2p plumbing (RCCL, or gloo in tests)
@@ -113,12 +101,12 @@ class _Merge:
     """Runs one rank's share of a merged prediction: forward of its placements in batches, accumulation into its strip of the
     mosaic, slab exchange with the neighbours, finalisation, gather of the requested output on rank 0."""
 
-    def __init__(self, model, places: np.ndarray, MH: int, MW: int, regression: bool, int8_merge: bool, rank: int, world: int, batch: int,
+    def __init__(self, model, places: np.ndarray, MH: int, MW: int, regression: bool, int8_merge: bool, rank: int, world: int,
                  blend: str = "mean"):
         self.model, self.dev = model, model._device
         self.C = model.n_out
         self.raw, self.int8 = bool(regression), bool(int8_merge)
-        self.rank, self.world, self.batch = rank, world, batch
+        self.rank, self.world = rank, world
         self.plan = MergePlan(places, MH, MW, world)
         self.lo, self.hi = self.plan.own[rank]
         rows = self.hi - self.lo
@@ -257,56 +245,33 @@ class _Merge:
         return full.cpu().numpy()
 
 
-class _TTAAccumulator:
-    """the dense fp32 NHWC accumulator [n_pad, h, w, C] of one call (re-made only when a batch of another tile size arrives)"""
-
-    def __init__(self, model, codes: Tuple[int, ...], raw: bool):
-        self.model, self.codes, self.raw = model, codes, raw
-        self.buf: Optional[torch.Tensor] = None
-
-    def run(self, wb: ops.WindowBatch, n: int, probs: Optional[torch.Tensor] = None, amax: Optional[torch.Tensor] = None) -> ops.TS:
-        """k forwards of the batch (ONE geometry: n_pad windows), the n real windows' outputs mapped back and averaged on the device;
-        the last launch also writes probs (NCHW) / amax (int64) when given"""
-        C = self.model.n_out
-        shape = (wb.n, wb.th, wb.tw, ops.rup4(C))
-        if self.buf is None or tuple(self.buf.shape) != shape:
-            self.buf = torch.empty(shape, dtype=torch.float32, device=self.model._device)
-        k = len(self.codes)
-        for i, g in enumerate(self.codes):
-            z = self.model.forward_windows_oriented(wb, g)
-            last = i == k - 1
-            ops.tta_accumulate(z, n, g, self.raw, i == 0, self.buf, k if last else 0, probs if last else None, amax if last else None)
-        return ops.TS(self.buf, 0, C)
-
-
 def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch, make_input: Callable, want, timing: Optional[dict] = None,
                tta: Optional[Tuple[int, ...]] = None, blend: str = "mean"):
     """make_input(first, n, n_pad) -> ops.WindowBatch of placements [first, first + n) padded to n_pad windows (so that every
     forward runs on ONE batch geometry and no second set of activation buffers is allocated).  tta: parsed codes -- every batch runs
     len(tta) forwards of that same geometry and the averaged probabilities take the place of the softmax in the merge.  blend: "mean" |
     "gaussian" (unet_amd/mosaic.py)"""
-    mg = _Merge(model, places, MH, MW, regression, int8_merge, rank, world, batch, blend)
-    acc = None if tta is None else _TTAAccumulator(model, tta, bool(regression))
+    mg = _Merge(model, places, MH, MW, regression, int8_merge, rank, world, blend)
     t0 = time.perf_counter()
-    done = 0
     batches = mg.plan.batches(rank, batch)
     n_pad = max((n for _, n in batches), default=0)
+    acc = None      # the dense fp32 NHWC TTA accumulator [n_pad, h, w, C] of the call (re-made only when a batch of another tile size arrives)
     for first, n in batches:
         wb = make_input(first, n, n_pad)
-        if acc is None:
-            z = model.forward_windows(wb)
-            mg.add_batch(first, n, z)
+        if tta is None:
+            mg.add_batch(first, n, model.forward_windows(wb))
         else:
-            mg.add_batch(first, n, acc.run(wb, n), values=True)
-        done += n
+            mean = model.forward_tta(wb, n, tta, bool(regression), acc)
+            acc = mean.buf
+            mg.add_batch(first, n, mean, values=True)
     mg.exchange()
     if timing is not None and not int8_merge and mg.hi > mg.lo:      # coverage of this rank's strip (before the division consumes nothing of it)
         timing.update(hits_min=int(mg.count.min().item()), hits_max=int(mg.count.max().item()))
     out = mg.finish(want)
     if timing is not None:
         torch.cuda.synchronize()
-        timing.update(seconds=time.perf_counter() - t0, windows_this_rank=done, windows=len(mg.plan.places), active_ranks=mg.plan.active,
-                      strip_rows=mg.hi - mg.lo, slab_floats_sent=0 if mg.sendbuf is None else mg.sendbuf.numel())
+        timing.update(seconds=time.perf_counter() - t0, windows_this_rank=sum(n for _, n in batches), windows=len(mg.plan.places),
+                      active_ranks=mg.plan.active, strip_rows=mg.hi - mg.lo, slab_floats_sent=0 if mg.sendbuf is None else mg.sendbuf.numel())
     return out
 
 
@@ -385,7 +350,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     check_blend(blend, large_file)
     model = getattr(model, "model", model)
     codes = tta_codes(tta, [(size, size)])
-    rank, local_rank, world = _dist_ctx()
+    rank, _, world = _dist_ctx()
     dev = model._device
     gt, tags = None, {}
     if isinstance(raster, (str, os.PathLike)):
@@ -394,7 +359,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
         nodata = meta.get("nodata") if nodata is None else nodata
         raster = arr[None] if arr.ndim == 2 else arr
     if isinstance(raster, np.ndarray):
-        raster = _torch_samples(raster)
+        raster = torch_samples(raster)
     if raster.dim() == 2:
         raster = raster[None]
     if raster.dtype not in ops.RASTER_TYPES:
@@ -435,18 +400,38 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
 
 # ----------------------------------------------------------------------------------------------- tile files: decode ahead of the GPU
 
-class _TilePrefetcher:
-    """A thread decodes the tile files of the coming batches into pinned host buffers; the main thread uploads the integer samples
-    (asynchronous copy) and cuts / scales them on the device.  Yields (first, n, pinned tensor [n_pad, C, h, w]); the consumer hands a
-    buffer back with the event recorded behind its upload, the producer waits for that event before it overwrites the buffer."""
+class _Prefetcher:
+    """What the prediction loops ask of a tile prefetcher.  Iteration yields (first, n, device buffer [n_pad, C, h, w]) per batch of tiles
+    [first, first + n), as the integer samples the files hold (rows beyond n: leftovers of an earlier batch, their windows are dropped);
+    done() after the last kernel that reads the buffer yielded last has been issued; close() -- or leaving the with block -- ends the decode
+    threads, also under a consumer that stops early."""
 
-    def __init__(self, tiles: Sequence[Path], batches: List[Tuple[int, int]], depth: int = 3):
-        self.tiles, self.batches = tiles, batches
+    def done(self):
+        pass
+
+    def close(self):
+        pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class _TilePrefetcher(_Prefetcher):
+    """A thread decodes the tile files of the coming batches into pinned host buffers; the main thread uploads the integer samples
+    (asynchronous copy) and cuts / scales them on the device.  A pinned buffer goes back to the producer with the event recorded behind its
+    upload, the producer waits for that event before it overwrites the buffer.  Serves tile sets of MIXED sizes (a batch is one size)."""
+
+    def __init__(self, tiles: Sequence[Path], batches: List[Tuple[int, int]], device, depth: int = 3):
+        self.tiles, self.batches, self.device = tiles, batches, device
         self.n_pad = max((n for _, n in batches), default=0)
         self.q: "queue.Queue" = queue.Queue(maxsize=depth)
         self.depth = depth
         self._free, self._made = {}, {}
         self.err = None
+        self._stop = False
         self.t = threading.Thread(target=self._work, daemon=True)
         self.t.start()
 
@@ -464,31 +449,27 @@ class _TilePrefetcher:
         # tile files are decoded by a small pool (file read, strip copies and the band de-interleave release the GIL), `depth` batches ahead
         from concurrent.futures import ThreadPoolExecutor
         try:
-            workers = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 2)))
-        except OSError:
-            workers = 4
-        try:
-            with ThreadPoolExecutor(max_workers=workers) as ex:
-                load = lambda path: np.ascontiguousarray(_as_samples(open_tile(path)))
+            with ThreadPoolExecutor(max_workers=min(8, default_workers())) as ex:
+                load = lambda path: torch_samples(open_tile(path))
                 pending, nxt = [], 0
                 for bi, (first, n) in enumerate(self.batches):
+                    if self._stop:
+                        break
                     while nxt < len(self.batches) and nxt <= bi + self.depth:
                         f0, n0 = self.batches[nxt]
                         pending.append([ex.submit(load, self.tiles[f0 + j]) for j in range(n0)])
                         nxt += 1
-                    arrs = [f.result() for f in pending.pop(0)]
-                    self._emit(first, n, arrs)
+                    self._emit(first, n, [f.result() for f in pending.pop(0)])
             self.q.put(None)
         except BaseException as e:      # noqa: BLE001  (surfaces in the consumer)
             self.err = e
             self.q.put(None)
 
-    def _emit(self, first, n, arrs):
-        a0 = arrs[0]
-        tdt = _torch_samples(a0[:0]).dtype
-        buf = self._buf((a0.shape, tdt), (self.n_pad,) + a0.shape, tdt)
-        for j, a in enumerate(arrs):
-            buf[j].copy_(_torch_samples(a))
+    def _emit(self, first, n, samples):
+        t0 = samples[0]
+        buf = self._buf((tuple(t0.shape), t0.dtype), (self.n_pad,) + tuple(t0.shape), t0.dtype)
+        for j, t in enumerate(samples):
+            buf[j].copy_(t)
         self.q.put((first, n, buf))
 
     def __iter__(self):
@@ -498,11 +479,12 @@ class _TilePrefetcher:
                 if self.err is not None:
                     raise self.err
                 return
-            yield it
+            first, n, buf = it
+            yield first, n, self._upload(buf)
 
-    def upload(self, buf: torch.Tensor, device) -> torch.Tensor:
-        """asynchronous host -> device copy of a yielded buffer; the buffer goes back to the producer behind the copy"""
-        d = buf.to(device, non_blocking=True)
+    def _upload(self, buf: torch.Tensor) -> torch.Tensor:
+        """asynchronous host -> device copy of a filled buffer; the buffer goes back to the producer behind the copy"""
+        d = buf.to(self.device, non_blocking=True)
         ev = None
         if d.is_cuda:
             ev = torch.cuda.Event()
@@ -510,32 +492,34 @@ class _TilePrefetcher:
         self._free[(tuple(buf.shape[1:]), buf.dtype)].put((buf, ev))
         return d
 
+    def close(self):
+        """the producer stops after the batch it is working on; what it still queues is dropped, so that it never waits on a full queue"""
+        self._stop = True
+        while self.t.is_alive():
+            with contextlib.suppress(queue.Empty):
+                self.q.get(timeout=0.05)
 
-class _FeedPrefetcher:
-    """The same interface on the training feed's machinery (unet_amd/feed.py): every pool task reads ONE tile file and copies it straight into
+
+class _FeedPrefetcher(_Prefetcher):
+    """The same on the training feed's machinery (unet_amd/feed.py): every pool task reads ONE tile file and copies it straight into
     its slot of a pinned staging buffer (the producer thread above copies the 16 tiles of a batch one after the other), uploads go out on a
     copy stream one batch ahead.  For tile sets of one height x width -- what split_raster writes (a tile with other bands or another sample
-    type makes the feeder raise); sets of mixed sizes keep _TilePrefetcher.
-    Yields (first, n, slot); `upload(slot, device)` returns the device buffer [n_pad, C, h, w] (rows beyond n: leftovers of an earlier batch,
-    their windows are dropped); `done(slot)` after the forward that reads it has been issued."""
+    type makes the feeder raise); sets of mixed sizes keep _TilePrefetcher."""
 
     def __init__(self, tiles: Sequence[Path], batches: List[Tuple[int, int]], device, depth: int = 3):
-        from unet_amd.feed import BatchFeeder
         self.tiles, self.batches = tiles, batches
         self.n_pad = max((n for _, n in batches), default=0)
-        self.feeder = BatchFeeder(lambda i: (_as_samples(open_tile(self.tiles[i])),), self.n_pad, device, depth=depth)
+        self.feeder = BatchFeeder(lambda i: (open_tile(self.tiles[i]),), self.n_pad, device, depth=depth)
+        self._slot = None           # the staging slot of the batch yielded last, until done()
 
     def __iter__(self):
-        for (first, n), slot in zip(self.batches, self.feeder.run([range(first, first + n) for first, n in self.batches])):
-            yield first, n, slot
+        for (first, n), self._slot in zip(self.batches, self.feeder.run([range(first, first + n) for first, n in self.batches])):
+            yield first, n, self._slot.dev[0]
 
-    @staticmethod
-    def upload(slot, device) -> torch.Tensor:
-        return slot.dev[0]
-
-    @staticmethod
-    def done(slot):
-        slot.release()
+    def done(self):
+        if self._slot is not None:
+            self._slot.release()
+            self._slot = None
 
     def close(self):
         self.feeder.close()
@@ -545,7 +529,21 @@ def _prefetcher(tiles, batches, sizes, device):
     """_FeedPrefetcher when every tile has the same height x width, else the general one"""
     if len(set(sizes)) == 1 and device.type == "cuda":
         return _FeedPrefetcher(tiles, batches, device)
-    return _TilePrefetcher(tiles, batches)
+    return _TilePrefetcher(tiles, batches, device)
+
+
+def _tile_windows(batch_size: int, device, div255_twice: bool) -> Callable:
+    """-> windows(d, n): a staged device buffer d [n_pad, C, h, w] whose first n tiles are real, as the checked ops.WindowBatch of its
+    n_pad whole tiles (window j = tile j from its corner).  The table of batch_size rows is uploaded once per call."""
+    zrows = [[0, 0, j, 0] for j in range(batch_size)]
+    ztab = ops.window_table(zrows, device)
+
+    def windows(d: torch.Tensor, n: int) -> ops.WindowBatch:
+        n_pad, _, h, w = d.shape
+        _check_batch(0, n, n_pad, len(zrows))
+        _check_windows(zrows[:n_pad], h, w, h, w, sources=n_pad)
+        return ops.WindowBatch(ops.WindowSource(d, div255_twice=div255_twice), ztab, 0, n_pad, h, w)
+    return windows
 
 
 def save_predictions(predict_model, predict_path, regression, merge=False, all_classes=False, specific_class=None, large_file=False,
@@ -553,10 +551,10 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
                      batch_invariant: bool = False, tta=None, blend: str = "mean"):
     """tta: None | "flips" | "d4" | a tuple of D4 codes (see predict_raster and unet_amd/tta.py), merged and per-tile outputs alike.
     blend: "mean" | "gaussian" (see predict_raster): how the windows of a merged prediction combine; only with merge=True (per-tile
-    outputs have no overlap) and not with large_file (ValueError before the model is loaded)"""
+    outputs have no overlap) and not with large_file (ValueError before the model is loaded).
+    validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
     check_blend(blend, large_file, merge)
     rank, local_rank, world = _dist_ctx()
-    dist = _dist()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model
     path = Path(predict_path)
@@ -567,75 +565,74 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     tiles = sorted([p for p in path.iterdir() if p.suffix.lower() in (".tif", ".tiff", ".npy")])
     if rank == 0:
         print(f"Started at: {time.strftime('%H:%M:%S')}  ({len(tiles)} tiles)")
-    dtype = learn.dls.train_ds.dtype
     geos = [_geo(t) for t in tiles]
     codes = tta_codes(tta, [(g[2], g[3]) for g in geos])
-    dev = model._device
-    C = model.n_out
-    div2 = dtype == "int16"
     t_start = time.perf_counter()
-
+    windows = _tile_windows(batch_size, model._device, learn.dls.train_ds.dtype == "int16")
     if merge:
-        # overlap merge (predict.py:257-355).  The extent follows from the tiles' geotransforms and sizes, which are known from the
-        # headers BEFORE any tile is predicted: every batch is accumulated into the device mosaic as soon as it is computed and its
-        # probabilities are dropped (the reference keeps all tiles' probabilities until the end).
-        if any(g[0] is None for g in geos):
-            raise ValueError("merge=True needs georeferenced tiles (.npy tiles carry no geotransform)")
-        gts = np.array([[g[0][0], g[3], g[0][1], g[0][3], g[2], g[0][5]] for g in geos], dtype=np.float64)
-        ulx_full, uly_full = gts[:, 0].min(), gts[:, 3].max()
-        xres, yres = gts[0, 2], gts[0, 5]
-        xmax_i, ymin_i = gts[:, 0].argmax(), gts[:, 3].argmin()
-        lrx_full = gts[:, 0].max() + gts[xmax_i, 1] * gts[xmax_i, 2]
-        lry_full = gts[:, 3].min() + gts[ymin_i, 4] * gts[ymin_i, 5]
-        if len(set(gts[:, 1])) != 1 or len(set(gts[:, 4])) != 1:
-            warnings.warn("Not all tiles have the same resolution.")
-        MW, MH = round((lrx_full - ulx_full) / xres), round((lry_full - uly_full) / yres)
-        int8_merge = bool(large_file and not regression)
+        out, gt = _save_merged(model, tiles, geos, windows, rank, world, regression, _want(regression, all_classes, specific_class),
+                               bool(large_file and not regression), batch_size, batch_invariant, codes, blend, timing)
+    else:
+        _save_tiles(model, tiles, geos, windows, rank, world, output_folder, regression, all_classes, specific_class, large_file, class_zero,
+                    batch_size, batch_invariant, codes)
+        if world > 1:
+            _dist().barrier()
+    if timing is not None:
+        timing["tiles_per_s_end_to_end"] = len(tiles) / (time.perf_counter() - t_start)
+    if not merge:
         if rank == 0:
-            print(f"True merged raster size: {C * MH * MW * (1 if int8_merge else 4) / (1024 ** 2): .1f}MB.")
-        places = np.array([[round((gts[i, 3] - uly_full) / yres), round((gts[i, 0] - ulx_full) / xres), geos[i][2], geos[i][3]]
-                           for i in range(len(tiles))], dtype=np.int64)
-        order = merge_order(places)
-        places, tiles_o = places[order], [tiles[i] for i in order]
-        plan = MergePlan(places, MH, MW, world)
-        pf = _prefetcher(tiles_o, plan.batches(rank, batch_size), [(int(p_[2]), int(p_[3])) for p_ in places], dev)
-        feed = iter(pf)
-        zrows = [[0, 0, j, 0] for j in range(batch_size)]
-        ztab = ops.window_table(zrows, dev)
-        held = []          # staging slot of the batch in flight: released once the NEXT batch is asked for (its gather has been issued by then)
+            print(f"Prediction stored in {output_folder}.")
+        return output_folder
+    if rank != 0:
+        return None
+    name = "_".join(filter(None, [AOI, year, model_name, "prediction"])) + ".tif"
+    store_tif(output_folder / name, out, gt, geos[0][1], -9999 if regression else None, class_zero)
+    print(f"Prediction stored in {output_folder}.")
+    return output_folder if regression else output_folder / name
 
+
+def _save_merged(model, tiles, geos, windows: Callable, rank, world, regression, want, int8_merge, batch_size, batch_invariant, codes, blend,
+                 timing):
+    """overlap merge (predict.py:257-355) of this rank's share of the tiles -> (merged array on rank 0, None elsewhere; geotransform of
+    the mosaic).  The extent follows from the tiles' geotransforms and sizes, which are known from the headers BEFORE any tile is
+    predicted: every batch is accumulated into the device mosaic as soon as it is computed and its probabilities are dropped (the
+    reference keeps all tiles' probabilities until the end)."""
+    if any(g[0] is None for g in geos):
+        raise ValueError("merge=True needs georeferenced tiles (.npy tiles carry no geotransform)")
+    gts = np.array([[g[0][0], g[3], g[0][1], g[0][3], g[2], g[0][5]] for g in geos], dtype=np.float64)
+    ulx_full, uly_full = gts[:, 0].min(), gts[:, 3].max()
+    xres, yres = gts[0, 2], gts[0, 5]
+    xmax_i, ymin_i = gts[:, 0].argmax(), gts[:, 3].argmin()
+    lrx_full = gts[:, 0].max() + gts[xmax_i, 1] * gts[xmax_i, 2]
+    lry_full = gts[:, 3].min() + gts[ymin_i, 4] * gts[ymin_i, 5]
+    if len(set(gts[:, 1])) != 1 or len(set(gts[:, 4])) != 1:
+        warnings.warn("Not all tiles have the same resolution.")
+    MW, MH = round((lrx_full - ulx_full) / xres), round((lry_full - uly_full) / yres)
+    if rank == 0:
+        print(f"True merged raster size: {model.n_out * MH * MW * (1 if int8_merge else 4) / (1024 ** 2): .1f}MB.")
+    places = np.array([[round((gts[i, 3] - uly_full) / yres), round((gts[i, 0] - ulx_full) / xres), geos[i][2], geos[i][3]]
+                       for i in range(len(tiles))], dtype=np.int64)
+    order = merge_order(places)
+    places, tiles_o = places[order], [tiles[i] for i in order]
+    plan = MergePlan(places, MH, MW, world)
+    sizes = [(int(p_[2]), int(p_[3])) for p_ in places]
+    # (the decode pool and its pinned ring live for one call)
+    with _prefetcher(tiles_o, plan.batches(rank, batch_size), sizes, model._device) as pf, contextlib.closing(iter(pf)) as feed:
         def make_input(first, n, n_pad):
-            while held:
-                pf.done(held.pop())
-            f, nn, buf = next(feed)
-            d = pf.upload(buf, dev)
+            pf.done()          # staging of the batch in flight: released once the NEXT batch is asked for (its gather has been issued by then)
+            f, nn, d = next(feed)
             assert (f, nn) == (first, n) and d.shape[0] == n_pad, ((f, nn, d.shape[0]), (first, n, n_pad))
-            _check_batch(0, n, n_pad, len(zrows))
-            _check_windows(zrows[:n_pad], d.shape[2], d.shape[3], d.shape[2], d.shape[3], sources=d.shape[0])
-            if hasattr(pf, "done"):
-                held.append(buf)
-            return ops.WindowBatch(ops.WindowSource(d, div255_twice=div2), ztab, 0, n_pad, d.shape[2], d.shape[3])
+            return windows(d, n)
 
-        want = _want(regression, all_classes, specific_class)
-        try:
-            with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):          # (see predict_raster)
-                out = _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch_size, make_input, want, timing, codes,
-                                 blend)
-        finally:
-            feed.close()
-            if hasattr(pf, "close"):
-                pf.close()              # (the decode pool and its pinned ring live for one call)
-        if timing is not None:
-            timing["tiles_per_s_end_to_end"] = len(tiles) / (time.perf_counter() - t_start)
-        if rank != 0:
-            return None
-        name = "_".join(filter(None, [AOI, year, model_name, "prediction"])) + ".tif"
-        store_tif(output_folder / name, out, [ulx_full, xres, 0.0, uly_full, 0.0, yres], geos[0][1], -9999 if regression else None,
-                  class_zero)
-        print(f"Prediction stored in {output_folder}.")
-        return output_folder if regression else output_folder / name
+        with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):          # (see predict_raster)
+            out = _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch_size, make_input, want, timing, codes, blend)
+    return out, [ulx_full, xres, 0.0, uly_full, 0.0, yres]
 
-    # ---- one output file per tile (predict.py:224-254); tile i -> rank i mod world
+
+def _save_tiles(model, tiles, geos, windows: Callable, rank, world, output_folder, regression, all_classes, specific_class, large_file,
+                class_zero, batch_size, batch_invariant, codes):
+    """one output file per tile (predict.py:224-254); tile i -> rank i mod world"""
+    dev, C = model._device, model.n_out
     mine = list(range(rank, len(tiles), world))
     sizes = [(geos[i][2], geos[i][3]) for i in mine]
     batches, i = [], 0
@@ -646,54 +643,32 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
         batches.append((i, n))
         i += n
     mtiles = [tiles[i] for i in mine]
-    pf = _prefetcher(mtiles, batches, sizes, dev)
-    zrows = [[0, 0, j, 0] for j in range(batch_size)]
-    ztab = ops.window_table(zrows, dev)
-    acc = None if codes is None else _TTAAccumulator(model, codes, bool(regression))
-    for first, n, buf in pf:
-        d = pf.upload(buf, dev)
-        _check_batch(0, n, d.shape[0], len(zrows))
-        _check_windows(zrows[:d.shape[0]], d.shape[2], d.shape[3], d.shape[2], d.shape[3], sources=d.shape[0])
-        wb = ops.WindowBatch(ops.WindowSource(d, div255_twice=div2), ztab, 0, d.shape[0], d.shape[2], d.shape[3])
-        h, w = d.shape[2], d.shape[3]
-        need_p = regression or all_classes or specific_class is not None
-        probs = torch.empty((n, C, h, w), dtype=torch.float32, device=dev) if need_p else None
-        amax = None if need_p else torch.empty((n, h, w), dtype=torch.int64, device=dev)
-        with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
-            if acc is None:
-                z = model.forward_windows(wb)
-            else:                # TTA: the finalising accumulate writes the mean probabilities (values) / their argmax
-                acc.run(wb, n, probs, amax)
-        if hasattr(pf, "done"):
-            pf.done(buf)               # (the gather that reads the staging buffer has been issued)
-        if acc is None:
-            zs = ops.TS(z.buf[:n], z.co, z.C)
-            if regression:       # predict.py:195-197: tile_preds[1] = raw outputs [1,H,W]
-                ops.nhwc_to_nchw(zs, probs)
-            else:
-                ops.softmax_argmax(zs, probs, amax)
-        outs = (probs if probs is not None else amax.to(torch.uint8)).cpu().numpy()
-        for j in range(n):
-            t = mtiles[first + j]
-            gt, tags = geos[mine[first + j]][0], geos[mine[first + j]][1]
-            if regression or all_classes:
-                out = outs[j]
-            elif specific_class is None:
-                out = outs[j]
-            else:
-                out = outs[j, specific_class]
-            if large_file and out.dtype.kind == "f" and out.max() <= 1 and (all_classes or specific_class):
-                out = np.around(out * LARGE_FILE_SCALE).astype(np.int8)
-            name = t.name if t.suffix != ".npy" else t.stem + ".tif"
-            store_tif(output_folder / name, out, gt, tags, None, class_zero)
-    if hasattr(pf, "close"):
-        pf.close()
-    if validation_vision:
-        pass  # per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope
-    if world > 1:
-        dist.barrier()
-    if timing is not None:
-        timing["tiles_per_s_end_to_end"] = len(tiles) / (time.perf_counter() - t_start)
-    if rank == 0:
-        print(f"Prediction stored in {output_folder}.")
-    return output_folder
+    need_p = regression or all_classes or specific_class is not None
+    acc = None      # the TTA accumulator, used again by every batch of the same tile size (see _run_merge)
+    with _prefetcher(mtiles, batches, sizes, dev) as pf:
+        for first, n, d in pf:
+            wb = windows(d, n)
+            h, w = d.shape[2], d.shape[3]
+            probs = torch.empty((n, C, h, w), dtype=torch.float32, device=dev) if need_p else None
+            amax = None if need_p else torch.empty((n, h, w), dtype=torch.int64, device=dev)
+            with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
+                if codes is None:
+                    z = model.forward_windows(wb)
+                else:                # TTA: the finalising accumulate writes the mean probabilities (values) / their argmax
+                    acc = model.forward_tta(wb, n, codes, bool(regression), acc, probs, amax).buf
+            pf.done()                  # (the gather that reads the staging buffer has been issued)
+            if codes is None:
+                zs = ops.TS(z.buf[:n], z.co, z.C)
+                if regression:       # predict.py:195-197: tile_preds[1] = raw outputs [1,H,W]
+                    ops.nhwc_to_nchw(zs, probs)
+                else:
+                    ops.softmax_argmax(zs, probs, amax)
+            outs = (probs if probs is not None else amax.to(torch.uint8)).cpu().numpy()
+            for j in range(n):
+                t = mtiles[first + j]
+                gt, tags = geos[mine[first + j]][0], geos[mine[first + j]][1]
+                out = outs[j] if regression or all_classes or specific_class is None else outs[j, specific_class]
+                if large_file and out.dtype.kind == "f" and out.max() <= 1 and (all_classes or specific_class):
+                    out = np.around(out * LARGE_FILE_SCALE).astype(np.int8)
+                name = t.name if t.suffix != ".npy" else t.stem + ".tif"
+                store_tif(output_folder / name, out, gt, tags, None, class_zero)

@@ -33,11 +33,10 @@ try:
     tiles = sorted(p for p in __import__("pathlib").Path(tiles_dir).iterdir())
     batches = [(i, min(16, len(tiles) - i)) for i in range(0, len(tiles), 16)]
     t0 = time.perf_counter()
-    pf = P._TilePrefetcher(tiles, batches)
     cnt = 0
-    for first, nn, buf in pf:
-        d = pf.upload(buf, torch.device("cuda"))
-        cnt += nn
+    with P._TilePrefetcher(tiles, batches, torch.device("cuda")) as pf:
+        for first, nn, d in pf:
+            cnt += nn
     torch.cuda.synchronize()
     print(f"prefetcher alone: {cnt / (time.perf_counter() - t0):.0f} tiles/s")
     tm = {}

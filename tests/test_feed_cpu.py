@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from unet_amd.feed import BatchFeeder, as_samples
+from unet_amd.feed import _SAMPLE_TYPES, BatchFeeder, as_samples, torch_samples
 
 
 def _load_factory(n, fail_at=None):
@@ -56,6 +56,23 @@ def test_sample_types_pass_or_go_through_int32():
     assert as_samples(np.zeros(3, np.int64)).dtype == np.int32
     assert as_samples(np.zeros(3, np.float64)).dtype == np.int32          # data.py:24: every tile is cast through int32 anyway
     assert as_samples(np.zeros(3, ">u2")).dtype == np.dtype("<u2")
+
+
+@pytest.mark.parametrize("dtype,staged", [(">u2", torch.uint16), (">i2", torch.int16), (">i4", torch.int32), (">f4", torch.float32),
+                                          ("<u2", torch.uint16), ("u1", torch.uint8), ("<i2", torch.int16), ("<i4", torch.int32),
+                                          ("<f4", torch.float32), ("i8", torch.int32), ("f8", torch.int32), (">i8", torch.int32),
+                                          (">f8", torch.int32)])
+def test_torch_samples_is_as_samples_as_a_contiguous_tensor(dtype, staged):
+    """the one staging function of prediction and the loader: any byte order, int64 / float64 through int32, band-interleaved views"""
+    vals = np.random.default_rng(5).integers(0, 30000, (5, 6, 3)) % (256 if np.dtype(dtype).itemsize == 1 else 30000)
+    vals = vals + 0.75 if np.dtype(dtype).kind == "f" and np.dtype(dtype).itemsize == 8 else vals      # float64 is truncated (data.py:24)
+    a = np.moveaxis(vals.astype(dtype), 2, 0)                     # [C, H, W] view of an interleaved [H, W, C] block: not contiguous
+    t = torch_samples(a)
+    want = as_samples(a)
+    assert want.dtype.byteorder in "=|<" and staged == _SAMPLE_TYPES[want.dtype]
+    assert t.dtype == staged and t.is_contiguous() and tuple(t.shape) == a.shape
+    assert t.numpy().tobytes() == np.ascontiguousarray(want).tobytes()
+    assert np.array_equal(t.numpy().astype(np.float64), np.trunc(a.astype(np.float64)))
 
 
 def test_flip_flags_are_the_draws_of_the_host_transforms():

@@ -73,7 +73,7 @@ def test_oriented_gather_equals_g_of_the_gather(rtype, dt):
     hi = {"u8": 256, "u16": 65535, "i16": 32767}[rtype]
     img = _raster(3, 3, 70, 90, npt, hi)
     import predict as P
-    data = P._torch_samples(img).cuda()
+    data = P.torch_samples(img).cuda()
     cs, co = (16, 5) if dt == torch.bfloat16 else (8, 3)          # a strided slice: lanes outside it stay untouched
     for div2 in (False, True):
         src = ops.WindowSource(data, div255_twice=div2)

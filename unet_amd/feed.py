@@ -37,6 +37,15 @@ def as_samples(a: np.ndarray) -> np.ndarray:
     return a if a.dtype in _SAMPLE_TYPES else a.astype(np.int32)
 
 
+def torch_samples(a: np.ndarray) -> torch.Tensor:
+    """as_samples(a) as a contiguous host tensor of the dtype _SAMPLE_TYPES names (shares memory with `a` where nothing had to change)"""
+    a = np.ascontiguousarray(as_samples(a))
+    # torch.from_numpy has no uint16 before 2.3: view the bits
+    t = torch.from_numpy(a.view(np.int16)).view(torch.uint16) if a.dtype == np.uint16 else torch.from_numpy(a)
+    assert t.dtype == _SAMPLE_TYPES[a.dtype]
+    return t
+
+
 def default_workers() -> int:
     try:
         n = len(os.sched_getaffinity(0))

@@ -413,31 +413,13 @@ class DataLoader:
     def _iter_direct(self, batches):
         """one batch, nothing to run ahead of: the items' INTEGER samples go up in one copy and are scaled / widened / flipped by the same
         kernels as the device feed (same bits as the host path), without threads or a staging ring"""
-        from .feed import _SAMPLE_TYPES, as_samples
-        has_y = self.ds.masks is not None
-        tfm = self.batch_tfm if has_y else None
-
-        def up(arrs):
-            a = np.ascontiguousarray(np.stack([as_samples(v) for v in arrs]))      # (tiles read as band-interleaved views stack into one C-ordered block)
-            t = torch.from_numpy(a.view(np.int16)).view(torch.uint16) if a.dtype == np.uint16 else torch.from_numpy(a)
-            assert t.dtype == _SAMPLE_TYPES[a.dtype]
-            return t.to(self.device)
+        from .feed import torch_samples
+        up = lambda arrs: torch_samples(np.stack(arrs)).to(self.device)     # (tiles read as band-interleaved views stack into one C-ordered block)
         with torch.cuda.device(self.device):
             for items in batches:
                 raws = [self.ds.raw(int(i)) for i in items]
-                n = len(raws)
-                flips = tfm.flip_flags(n) if hasattr(tfm, "flip_flags") else None
-                src = up([r[0] for r in raws])
-                xb = torch.empty(src.shape, dtype=torch.float32, device=self.device)
-                ops.tiles_stage(src, self.ds.dtype == "int16", xb, flips)
-                yb = None
-                if has_y:
-                    msk = up([r[1] for r in raws])
-                    yb = torch.empty(msk.shape, dtype=torch.float32 if self.ds.regression else torch.int64, device=self.device)
-                    ops.mask_stage(msk, yb, flips)
-                if tfm is not None and flips is None:
-                    xb, yb = tfm(xb, yb)
-                yield xb, yb
+                msk = up([r[1] for r in raws]) if self.ds.masks is not None else None
+                yield self._stage(up([r[0] for r in raws]), msk)
 
     def _iter_device(self, batches):
         from .feed import BatchFeeder
@@ -445,24 +427,27 @@ class DataLoader:
             raise RuntimeError("feed='device' stages batches for the HIP kernels: it needs a GPU loader (device='cuda')")
         if self._feeder is None or self._feeder.load.__self__ is not self.ds:
             self._feeder = BatchFeeder(self.ds.raw, self.bs, self.device, depth=self.depth, workers=self.workers)
-        has_y = self.ds.masks is not None
-        div2 = self.ds.dtype == "int16"
-        tfm = self.batch_tfm if has_y else None
         with torch.cuda.device(self.device):
             for slot in self._feeder.run(batches):
                 n = slot.n
-                flips = tfm.flip_flags(n) if hasattr(tfm, "flip_flags") else None       # flips run inside the staging kernels
-                src = slot.dev[0][:n]
-                xb = torch.empty(src.shape, dtype=torch.float32, device=self.device)
-                ops.tiles_stage(src, div2, xb, flips)
-                yb = None
-                if has_y:
-                    yb = torch.empty(slot.dev[1][:n].shape, dtype=torch.float32 if self.ds.regression else torch.int64, device=self.device)
-                    ops.mask_stage(slot.dev[1][:n], yb, flips)
-                slot.release()
-                if tfm is not None and flips is None:
-                    xb, yb = tfm(xb, yb)
-                yield xb, yb
+                batch = self._stage(slot.dev[0][:n], slot.dev[1][:n] if self.ds.masks is not None else None)
+                slot.release()      # (the kernels that read the slot's device buffers have been issued)
+                yield batch
+
+    def _stage(self, src: torch.Tensor, msk: Optional[torch.Tensor]):
+        """integer batch on the device (+ its mask batch) -> (xb fp32 [B,C,H,W], yb): scaled / widened by the staging kernels, which also run
+        the flips of a batch transform that is flips only; any other batch transform runs on the staged batch"""
+        tfm = self.batch_tfm if msk is not None else None
+        flips = tfm.flip_flags(src.shape[0]) if hasattr(tfm, "flip_flags") else None       # flips run inside the staging kernels
+        xb = torch.empty(src.shape, dtype=torch.float32, device=self.device)
+        ops.tiles_stage(src, self.ds.dtype == "int16", xb, flips)
+        yb = None
+        if msk is not None:
+            yb = torch.empty(msk.shape, dtype=torch.float32 if self.ds.regression else torch.int64, device=self.device)
+            ops.mask_stage(msk, yb, flips)
+        if tfm is not None and flips is None:
+            xb, yb = tfm(xb, yb)
+        return xb, yb
 
 
 class DataLoaders:

@@ -583,19 +583,31 @@ class HipDynamicUnet(nn.Module):
         return probs, amax
 
     def _predict_tta(self, x: torch.Tensor, tta, raw: bool, want_probs: bool, want_argmax: bool):
-        """k eager forwards of the oriented batch, each mapped back and added in code order on the device (unet_tta_accumulate); the
-        last launch divides by k and writes the NCHW output / argmax"""
+        """predict_values / predict_probs with a TTA set: the NCHW output / argmax of forward_tta over the whole batch"""
         from .tta import parse
         N, _, H, W = x.shape
-        codes = parse(tta, [(H, W)])
-        acc = torch.empty((N, H, W, ops.rup4(self.n_out)), dtype=torch.float32, device=self._device)
         probs = torch.empty((N, self.n_out, H, W), dtype=torch.float32, device=self._device) if want_probs else None
         amax = torch.empty((N, H, W), dtype=torch.int64, device=self._device) if want_argmax and not raw else None
+        self.forward_tta(x, N, parse(tta, [(H, W)]), raw, probs=probs, amax=amax)
+        return probs, amax
+
+    @torch.no_grad()
+    def forward_tta(self, x, n: int, codes, raw: bool, acc: Optional[torch.Tensor] = None, probs: Optional[torch.Tensor] = None,
+                    amax: Optional[torch.Tensor] = None) -> TS:
+        """k = len(codes) eager forwards of ONE geometry on the oriented batch x (fp32 NCHW tensor or ops.WindowBatch; codes: parsed D4
+        codes, unet_amd/tta.py), the first n windows' outputs mapped back and added in code order on the device (unet_tta_accumulate); the
+        last launch divides by k and also writes probs (NCHW) / amax (int64) when given.  Returns the fp32 NHWC accumulator [N, H, W, C]
+        holding the mean probabilities (raw: values); acc: the accumulator of an earlier call, used again when its shape fits."""
+        N, H, W = (x.n, x.th, x.tw) if isinstance(x, ops.WindowBatch) else (x.shape[0], x.shape[2], x.shape[3])
+        shape = (N, H, W, ops.rup4(self.n_out))
+        if acc is None or tuple(acc.shape) != shape:
+            acc = torch.empty(shape, dtype=torch.float32, device=self._device)
+        k = len(codes)
         for i, g in enumerate(codes):
             z = self._hip_forward(x, False, orient=g)
-            last = i == len(codes) - 1
-            ops.tta_accumulate(z, N, g, raw, i == 0, acc, len(codes) if last else 0, probs if last else None, amax if last else None)
-        return probs, amax
+            last = i == k - 1
+            ops.tta_accumulate(z, n, g, raw, i == 0, acc, k if last else 0, probs if last else None, amax if last else None)
+        return TS(acc, 0, self.n_out)
 
     @torch.no_grad()
     def forward_windows(self, wb: "ops.WindowBatch") -> TS:
