@@ -477,6 +477,55 @@ int unet_warp_affine(const float* src, float* dst, int n, int C, int H, int W, c
 int unet_warp_affine_mask(const void* src, void* dst, int dst_f32, int n, int H, int W, const float* inv_maps_host, int border, double fill,
                           void* stream);
 
+/* -------------------------------------------------- pixel-level augmentation --
+ * The radiometric augmentations of unet_amd.augment (albumentations RandomBrightnessContrast, CoarseDropout, RandomGamma, GaussNoise,
+ * ChannelDropout, ChannelShuffle, GaussianBlur, Blur) on a device batch [n, C, H, W] fp32 (csrc/pixel_aug.hip).  Per-image parameters
+ * are read at call time from host memory and passed in the kernel arguments; no device allocation, no host wait, no atomics; each
+ * thread stores only its own output elements.
+ *
+ * unet_pixel_ops, IN PLACE: image progs[j].image gets the program progs[j].ops[0 .. nops), applied in order to every pixel; images
+ * without an entry are not touched (no block is launched for them).  nprog <= UNET_PIXEL_MAX_PROGS per call, image indices strictly
+ * increasing.  Operands of an op (code & 0xff; f0, f1 fp32; u0, u1 uint32):
+ *   BRIGHTNESS_CONTRAST  x = clamp(x * f0 [+ f1], 0, 1): product and sum rounded separately, the sum skipped when f1 == 0
+ *   GAMMA                x = powf(fmaxf(x, 0), f0)
+ *   GAUSS_NOISE          x = clamp(x + f0 + f1 z, 0, 1); z = the normal deviate of element e under the Philox4x32-10 key (u0, u1):
+ *                        counter (e / 4, 0, 0, 0); word w -> u = ((w >> 8) + 0.5) 2^-24; words (0, 1) give r cos(2 pi u1), r sin(2 pi u1)
+ *                        with r = sqrt(-2 ln u0) for elements 4q, 4q + 1, words (2, 3) the same for 4q + 2, 4q + 3.
+ *                        e = (c H + y) W + x with UNET_PIXEL_PER_CHANNEL set in code, else y W + x (one deviate for all channels)
+ *   FILL_RECTS           x = f0 inside any of rects[u0 .. u0 + u1): rows [y0, y1) x columns [x0, x1), every channel
+ *   CHANNEL_DROP         x = f0 in the channels whose bit is set in u0
+ *   CHANNEL_PERMUTE      channel c takes the value of channel (u0 | u1 << 32) >> 4 c & 15; C <= 16
+ * unet_fill_rects_mask: the rectangles of sets[j] of mask sets[j].image set to fill; mask [n, H, W] int64 (dst_f32 = 0) or fp32 (1).
+ * unet_blur_separable, OUT OF PLACE: dst[j] = src[j] filtered along rows and columns with the ksize[j] (odd, 1..31) taps
+ * taps_host[31 j ..], border cv2 reflect-101 repeated as often as the radius needs (any H, W >= 1); ksize 1 with tap 1 copies bit for
+ * bit.  n <= UNET_BLUR_MAX_IMAGES per call.
+ * All return -1 before any launch on a null pointer, sizes or counts out of range, an unknown opcode, a non-finite operand, a
+ * channel index >= C, or src == dst (blur). */
+#define UNET_PIXEL_MAX_PROGS 8
+#define UNET_PIXEL_MAX_OPS 8
+#define UNET_PIXEL_MAX_RECTS 32
+#define UNET_BLUR_MAX_IMAGES 16
+#define UNET_BLUR_MAX_KSIZE 31
+enum { UNET_PIXEL_BRIGHTNESS_CONTRAST = 1, UNET_PIXEL_GAMMA = 2, UNET_PIXEL_GAUSS_NOISE = 3, UNET_PIXEL_FILL_RECTS = 4,
+       UNET_PIXEL_CHANNEL_DROP = 5, UNET_PIXEL_CHANNEL_PERMUTE = 6, UNET_PIXEL_PER_CHANNEL = 0x100 };
+typedef struct unet_pixel_op {
+    uint32_t code, u0, u1;
+    float f0, f1;
+} unet_pixel_op;
+typedef struct unet_pixel_prog {
+    uint32_t image, nops, nrects, reserved;
+    unet_pixel_op ops[UNET_PIXEL_MAX_OPS];
+    uint16_t rects[UNET_PIXEL_MAX_RECTS][4];           /* y0, x0, y1, x1 */
+} unet_pixel_prog;
+typedef struct unet_rect_set {
+    uint32_t image, nrects;
+    uint16_t rects[UNET_PIXEL_MAX_RECTS][4];
+} unet_rect_set;
+int unet_pixel_ops(float* x, int n, int C, int H, int W, const unet_pixel_prog* progs_host, int nprog, void* stream);
+int unet_fill_rects_mask(void* mask, int dst_f32, int n, int H, int W, const unet_rect_set* sets_host, int nsets, double fill, void* stream);
+int unet_blur_separable(const float* src, float* dst, int n, int C, int H, int W, const int* ksize_host, const float* taps_host,
+                        void* stream);
+
 /* ---------------------------------------------------- bf16-storage twins --
  * The HBM-bound kernels of the step with bf16 activation / gradient tensors (per-channel vectors, statistics, indices, losses stay
  * as in the fp32 entry point of the same name; arithmetic is fp32 per element, one rounding to bf16 at the store).  Used by

@@ -84,6 +84,25 @@ class WgradDesc(C.Structure):
     ]
 
 
+PIXEL_MAX_PROGS, PIXEL_MAX_OPS, PIXEL_MAX_RECTS, BLUR_MAX_IMAGES, BLUR_MAX_KSIZE = 8, 8, 32, 16, 31
+PIXEL_BRIGHTNESS_CONTRAST, PIXEL_GAMMA, PIXEL_GAUSS_NOISE, PIXEL_FILL_RECTS, PIXEL_CHANNEL_DROP, PIXEL_CHANNEL_PERMUTE = 1, 2, 3, 4, 5, 6
+PIXEL_PER_CHANNEL = 0x100
+
+
+class PixelOp(C.Structure):
+    _fields_ = [("code", C.c_uint32), ("u0", C.c_uint32), ("u1", C.c_uint32), ("f0", C.c_float), ("f1", C.c_float)]
+
+
+class PixelProg(C.Structure):
+    """unet_pixel_prog: the pointwise program of one image (include/unet_hip.h)"""
+    _fields_ = [("image", C.c_uint32), ("nops", C.c_uint32), ("nrects", C.c_uint32), ("reserved", C.c_uint32),
+                ("ops", PixelOp * PIXEL_MAX_OPS), ("rects", (C.c_uint16 * 4) * PIXEL_MAX_RECTS)]
+
+
+class RectSet(C.Structure):
+    _fields_ = [("image", C.c_uint32), ("nrects", C.c_uint32), ("rects", (C.c_uint16 * 4) * PIXEL_MAX_RECTS)]
+
+
 class PackJob(C.Structure):
     _fields_ = [("w", vp), ("wp", vp), ("Cout", C.c_int), ("Cin", C.c_int), ("ks", C.c_int), ("mode", C.c_int), ("out_scale", vp)]
 
@@ -182,6 +201,9 @@ _sig = {
     "unet_dice_counts": (i, [vp, vp, ll, i, vp, vp]),
     "unet_warp_affine": (i, [vp, vp, i, i, i, i, c_float_p, i, i, f, vp]),
     "unet_warp_affine_mask": (i, [vp, vp, i, i, i, i, c_float_p, i, C.c_double, vp]),
+    "unet_pixel_ops": (i, [vp, i, i, i, i, vp, i, vp]),
+    "unet_fill_rects_mask": (i, [vp, i, i, i, i, vp, i, C.c_double, vp]),
+    "unet_blur_separable": (i, [vp, vp, i, i, i, i, C.POINTER(C.c_int), c_float_p, vp]),
     "unet_window_gather_oriented": (i, [vp, i, i, ll, ll, i, vp, i, i, i, i, vp, i, i, i, i, vp]),
     "unet_nchw_to_nhwc_oriented": (i, [vp, vp, i, i, i, i, i, i, i, i, vp]),
     "unet_tta_accumulate": (i, [vp, i, i, i, i, i, i, i, i, i, vp, i, i, vp, vp, vp]),

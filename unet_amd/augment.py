@@ -16,6 +16,17 @@ rotated about (W / 2, H / 2).  Known difference: bilinear weights are fp32, with
 the transform's interpolation (0 nearest, 1 bilinear), masks always nearest (floor(s + 0.5)); border modes are cv2's 0 constant,
 1 replicate, 2 reflect and 4 reflect-101.  Wrap borders, bicubic interpolation, ``crop_border=True`` and per-channel fill values are
 refused with NotImplementedError.
+
+Pixel-level transforms (``RandomBrightnessContrast``, ``CoarseDropout``, ``RandomGamma``, ``GaussNoise``, ``ChannelDropout``,
+``ChannelShuffle``) are pointwise: ``BatchAugment`` turns each maximal run of them into one short program per fired image and runs the
+programs of the whole batch in one launch (``unet_pixel_ops``, csrc/pixel_aug.hip).  ``GaussianBlur`` and ``Blur`` are one separable
+filter launch (``unet_blur_separable``, border reflect-101 as cv2's default).  Masks are untouched by all of them (``CoarseDropout``
+with ``mask_fill_value`` aside).  The Gaussian noise is a pure function of two key words drawn from the seeded generator and the element
+index (Philox4x32-10 and Box-Muller, include/unet_hip.h), so it does not depend on how the batch is split into launches.  Known
+difference: ``GaussNoise.var_limit`` and ``mean`` are on the 8-bit scale the defaults (10 - 50) are meant for -- on the [0, 1] batches
+here sigma = sqrt(var) / 255 and mean / 255; older albumentations releases applied the unscaled sigma to float images.  A scalar
+``GaussianBlur.blur_limit`` v means kernel sizes 3..v (what albumentations makes of it when ``sigma_limit`` is 0); a ``blur_limit`` that
+holds 0 (kernel size from sigma) or an even bound, and kernel sizes above 31, are refused with NotImplementedError.
 """
 from __future__ import annotations
 
@@ -30,6 +41,8 @@ class _Transform:
     """A transform fires with probability ``p`` (drawn first); only then are its parameters drawn (``get_params``) and applied
     (``apply_params``).  The split lets ``BatchAugment`` draw a whole batch before anything runs."""
 
+    channels = False             # True: get_params takes the number of channels as well (ChannelDropout, ChannelShuffle)
+
     def __init__(self, p: float = 0.5, always_apply: bool = False):
         self.p = 1.0 if always_apply else float(p)
 
@@ -37,11 +50,14 @@ class _Transform:
         """the random parameters of one application to an H x W image (none by default)"""
         return None
 
+    def draw_params(self, g: np.random.Generator, C, H: int, W: int):
+        return self.get_params(g, H, W, C) if self.channels else self.get_params(g, H, W)
+
     def apply_params(self, img: torch.Tensor, mask: torch.Tensor, prm) -> Tuple[torch.Tensor, torch.Tensor]:
         raise NotImplementedError
 
     def apply(self, img: torch.Tensor, mask: torch.Tensor, g: np.random.Generator) -> Tuple[torch.Tensor, torch.Tensor]:
-        return self.apply_params(img, mask, self.get_params(g, *img.shape[-2:]))
+        return self.apply_params(img, mask, self.draw_params(g, img.shape[-3] if img.dim() >= 3 else 1, *img.shape[-2:]))
 
     def __call__(self, img, mask, g):
         return self.apply(img, mask, g) if g.random() < self.p else (img, mask)
@@ -210,7 +226,33 @@ def _warp(img: torch.Tensor, mask, inv_maps: np.ndarray, interp: int, border: in
     return out, mout
 
 
-class RandomBrightnessContrast(_Transform):
+class _Pointwise(_Transform):
+    """a transform of each pixel on its own: ``program`` gives its ops for ``ops.pixel_ops`` (None: it needs the whole image and runs per
+    image), ``mask_rects`` the (rectangles, fill) it sets in the mask, if any"""
+
+    def program(self, prm, C: int, H: int, W: int):
+        raise NotImplementedError
+
+    def mask_rects(self, prm):
+        return None
+
+    def check(self, C: int, H: int, W: int):
+        """raises for an image this transform cannot take"""
+
+    def _cpu(self, img: torch.Tensor, prm) -> torch.Tensor:
+        raise NotImplementedError
+
+    def apply_params(self, img, mask, prm):
+        self.check(img.shape[-3], *img.shape[-2:])
+        if not img.is_cuda:
+            return self._cpu(img, prm), mask
+        from . import ops
+        out = img.contiguous().clone()[None]
+        ops.pixel_ops(out, {0: self.program(prm, *out.shape[1:])})
+        return out[0], mask
+
+
+class RandomBrightnessContrast(_Pointwise):
     """albumentations ``RandomBrightnessContrast(brightness_limit, contrast_limit, brightness_by_max=True, p)`` on a float image in
     [0, 1]: ``img * alpha + beta * (1 if brightness_by_max else mean(img))`` with alpha = 1 + U(contrast_limit), beta = U(brightness_limit),
     clipped to [0, 1]; the mask is untouched."""
@@ -231,8 +273,11 @@ class RandomBrightnessContrast(_Transform):
             out = out + (beta if self.by_max else beta * img.mean())
         return out.clamp_(0.0, 1.0), mask
 
+    def program(self, prm, C, H, W):
+        return [("bc", prm[0], prm[1])] if self.by_max else None
 
-class CoarseDropout(_Transform):
+
+class CoarseDropout(_Pointwise):
     """albumentations ``CoarseDropout(max_holes=8, max_height=8, max_width=8, min_holes=None, min_height=None, min_width=None,
     fill_value=0, mask_fill_value=None, p)``: between min_holes and max_holes rectangles of the image set to fill_value (the mask
     only when mask_fill_value is given); the unset minima default to the maxima."""
@@ -263,6 +308,234 @@ class CoarseDropout(_Transform):
                 mask[y1:y1 + hh, x1:x1 + ww] = self.mask_fill
         return img, mask
 
+    def program(self, holes, C, H, W):
+        return [("rects", [(y1, x1, y1 + hh, x1 + ww) for y1, x1, hh, ww in holes if hh > 0 and ww > 0], self.fill)]
+
+    def mask_rects(self, holes):
+        if self.mask_fill is None:
+            return None
+        return [(y1, x1, y1 + hh, x1 + ww) for y1, x1, hh, ww in holes if hh > 0 and ww > 0], self.mask_fill
+
+
+def _range(v, low) -> Tuple[float, float]:
+    """albumentations ``to_tuple(v, low)``: a scalar v means (low, v)"""
+    return (float(low), float(v)) if np.isscalar(v) else (float(v[0]), float(v[1]))
+
+
+class RandomGamma(_Pointwise):
+    """albumentations ``RandomGamma(gamma_limit=(80, 120), p)``: ``img ** gamma`` with gamma = U(gamma_limit) / 100"""
+
+    def __init__(self, gamma_limit=(80, 120), p=0.5, always_apply=False):
+        super().__init__(p, always_apply)
+        self.limit = _range(gamma_limit, gamma_limit)
+
+    def get_params(self, g, H, W):
+        return float(g.uniform(*self.limit)) / 100.0
+
+    def program(self, gamma, C, H, W):
+        return [("gamma", gamma)]
+
+    def _cpu(self, img, gamma):
+        return img.clamp(min=0.0).double().pow(gamma).float()
+
+
+PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+
+
+def philox4x32_10(counter: np.ndarray, key) -> np.ndarray:
+    """Philox4x32-10 on counters [..., 4] (uint32) under the two key words: [..., 4] uint32"""
+    c = [np.asarray(counter[..., k], dtype=np.uint64) for k in range(4)]
+    k0, k1 = int(key[0]) & 0xffffffff, int(key[1]) & 0xffffffff
+    m32 = np.uint64(0xffffffff)
+    for _ in range(10):
+        p0, p1 = np.uint64(PHILOX_M[0]) * c[0], np.uint64(PHILOX_M[1]) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & m32]
+        k0, k1 = (k0 + PHILOX_W[0]) & 0xffffffff, (k1 + PHILOX_W[1]) & 0xffffffff
+    return np.stack(c, axis=-1).astype(np.uint32)
+
+
+def normal_field(key, count: int) -> np.ndarray:
+    """the normal deviates of elements 0 .. count - 1 under a key (fp64): words (0, 1) of counter (q, 0, 0, 0) give elements 4q, 4q + 1 as
+    r cos(2 pi u1), r sin(2 pi u1), r = sqrt(-2 ln u0), words (2, 3) elements 4q + 2, 4q + 3; u = ((w >> 8) + 0.5) 2^-24"""
+    nq = -(-count // 4)
+    ctr = np.zeros((nq, 4), dtype=np.uint32)
+    ctr[:, 0] = np.arange(nq, dtype=np.uint32)
+    u = ((philox4x32_10(ctr, key) >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+    r = np.sqrt(-2.0 * np.log(u[:, 0::2]))                          # [nq, 2]: from words 0 and 2
+    th = 2.0 * np.pi * u[:, 1::2]
+    return np.stack([r * np.cos(th), r * np.sin(th)], axis=-1).reshape(-1)[:count]
+
+
+class GaussNoise(_Pointwise):
+    """albumentations ``GaussNoise(var_limit=(10, 50), mean=0, per_channel=True, p)``: ``clip(img + N(mean, var))`` with var =
+    U(var_limit), var and mean on the 8-bit scale (sigma = sqrt(var) / 255 on a [0, 1] image); per_channel=False adds one field to every
+    channel.  The parameters are (var, key word 0, key word 1)."""
+
+    def __init__(self, var_limit=(10.0, 50.0), mean=0, per_channel=True, p=0.5, always_apply=False):
+        super().__init__(p, always_apply)
+        self.var = _range(var_limit, 0)
+        if self.var[0] < 0 or self.var[1] < self.var[0]:
+            raise ValueError(f"GaussNoise: var_limit {var_limit!r} must be a non-negative range")
+        self.mean, self.per_channel = float(mean), bool(per_channel)
+
+    def get_params(self, g, H, W):
+        var = float(g.uniform(*self.var))
+        return var, int(g.integers(0, 2 ** 32)), int(g.integers(0, 2 ** 32))
+
+    def program(self, prm, C, H, W):
+        var, k0, k1 = prm
+        return [("noise", k0, k1, self.mean / 255.0, math.sqrt(var) / 255.0, self.per_channel)]
+
+    def _cpu(self, img, prm):
+        var, k0, k1 = prm
+        C, H, W = img.shape
+        z = normal_field((k0, k1), C * H * W).reshape(C, H, W) if self.per_channel else normal_field((k0, k1), H * W).reshape(1, H, W)
+        out = img.double() + self.mean / 255.0 + math.sqrt(var) / 255.0 * torch.from_numpy(z)
+        return out.clamp_(0.0, 1.0).float()
+
+
+class ChannelDropout(_Pointwise):
+    """albumentations ``ChannelDropout(channel_drop_range=(1, 1), fill_value=0, p)``: a number of channels in the range, drawn without
+    replacement, set to fill_value"""
+    channels = True
+
+    def __init__(self, channel_drop_range=(1, 1), fill_value=0, p=0.5, always_apply=False):
+        super().__init__(p, always_apply)
+        self.range = (int(channel_drop_range[0]), int(channel_drop_range[1]))
+        if not 1 <= self.range[0] <= self.range[1]:
+            raise ValueError(f"Invalid channel_drop_range. Got: {channel_drop_range}")
+        self.fill = fill_value
+
+    def check(self, C, H, W):
+        if C == 1:
+            raise ValueError("Images has one channel. ChannelDropout is not defined.")
+        if self.range[1] >= C:
+            raise ValueError("Can not drop all channels in ChannelDropout.")
+
+    def get_params(self, g, H, W, C):
+        self.check(C, H, W)
+        count = int(g.integers(self.range[0], self.range[1] + 1))
+        return [int(c) for c in g.choice(C, size=count, replace=False)]
+
+    def program(self, drop, C, H, W):
+        return [("drop", drop, self.fill)]
+
+    def _cpu(self, img, drop):
+        out = img.clone()
+        out[list(drop)] = self.fill
+        return out
+
+
+class ChannelShuffle(_Pointwise):
+    """albumentations ``ChannelShuffle(p)``: the channels in a random order, channel c taking channel perm[c]"""
+    channels = True
+
+    def check(self, C, H, W):
+        if C > 16:
+            raise ValueError(f"ChannelShuffle: at most 16 channels are supported, the image has {C}")
+
+    def get_params(self, g, H, W, C):
+        self.check(C, H, W)
+        return [int(c) for c in g.permutation(C)]
+
+    def program(self, perm, C, H, W):
+        return [("permute", perm)]
+
+    def _cpu(self, img, perm):
+        return img[list(perm)].clone()
+
+
+def gaussian_taps(k: int, sigma: float) -> np.ndarray:
+    """cv2 ``getGaussianKernel(k, sigma)`` as fp32: the fixed tables for sigma <= 0 and k in 1, 3, 5, 7; else exp(-x^2 / (2 sigma^2)) with
+    sigma = 0.3 ((k - 1) / 2 - 1) + 0.8 when it is not given, normalised in fp64"""
+    small = {1: [1.0], 3: [0.25, 0.5, 0.25], 5: [0.0625, 0.25, 0.375, 0.25, 0.0625],
+             7: [0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125]}
+    if sigma <= 0 and k in small:
+        return np.array(small[k], dtype=np.float32)
+    if sigma <= 0:
+        sigma = 0.3 * ((k - 1) * 0.5 - 1.0) + 0.8
+    x = np.arange(k, dtype=np.float64) - (k - 1) * 0.5
+    t = np.exp(-(x * x) / (2.0 * sigma * sigma))
+    return (t / t.sum()).astype(np.float32)
+
+
+MAX_BLUR = 31
+
+
+def _reflect101(i: np.ndarray, N: int) -> np.ndarray:
+    if N == 1:
+        return np.zeros_like(i)
+    r = np.mod(i, 2 * N - 2)
+    return np.where(r < N, r, 2 * N - 2 - r)
+
+
+class _Blur(_Transform):
+    """a separable filter with per-image taps: kernel sizes are the odd numbers in blur_limit"""
+
+    def __init__(self, blur_limit, p, always_apply):
+        super().__init__(p, always_apply)
+        name = type(self).__name__
+        lo, hi = (3, int(blur_limit)) if np.isscalar(blur_limit) else (int(blur_limit[0]), int(blur_limit[1]))
+        if lo == 0 or hi == 0 or lo % 2 == 0 or hi % 2 == 0:
+            raise NotImplementedError(f"{name}: blur_limit={blur_limit!r} is not supported (odd bounds; 0, the kernel size from sigma, is not)")
+        if lo < 1 or hi < lo:
+            raise ValueError(f"{name}: blur_limit={blur_limit!r} is not a range of kernel sizes")
+        if hi > MAX_BLUR:
+            raise NotImplementedError(f"{name}: kernel sizes above {MAX_BLUR} are not supported (blur_limit={blur_limit!r})")
+        self.blur = (lo, hi)
+
+    def ksize(self, g) -> int:
+        return self.blur[0] + 2 * int(g.integers(0, (self.blur[1] - self.blur[0]) // 2 + 1))
+
+    def taps(self, prm) -> np.ndarray:
+        raise NotImplementedError
+
+    def apply_params(self, img, mask, prm):
+        taps = self.taps(prm)
+        if img.is_cuda:
+            from . import ops
+            src = img.contiguous()[None]
+            out = torch.empty_like(src)
+            ops.blur_separable(src, out, [taps])
+            return out[0], mask
+        C, H, W = img.shape
+        r, t = len(taps) // 2, taps.astype(np.float64)
+        x = img.double().numpy()
+        cols = _reflect101(np.arange(W)[:, None] + np.arange(-r, r + 1)[None], W)       # [W, k]
+        rows = _reflect101(np.arange(H)[:, None] + np.arange(-r, r + 1)[None], H)       # [H, k]
+        x = (x[:, :, cols] * t).sum(-1)
+        x = (x[:, rows, :] * t[None, None, :, None]).sum(2)
+        return torch.from_numpy(x).float(), mask
+
+
+class GaussianBlur(_Blur):
+    """albumentations ``GaussianBlur(blur_limit=(3, 7), sigma_limit=0, p)``: cv2.GaussianBlur with a kernel size uniform over the odd
+    sizes in blur_limit and sigma = U(sigma_limit) (a scalar v means (0, v); sigma 0: cv2's rule for the size), border reflect-101"""
+
+    def __init__(self, blur_limit=(3, 7), sigma_limit=0, p=0.5, always_apply=False):
+        super().__init__(blur_limit, p, always_apply)
+        self.sigma = _range(sigma_limit, 0)
+
+    def get_params(self, g, H, W):
+        return self.ksize(g), float(g.uniform(*self.sigma))
+
+    def taps(self, prm):
+        return gaussian_taps(*prm)
+
+
+class Blur(_Blur):
+    """albumentations ``Blur(blur_limit=7, p)``: a k x k box filter, k uniform over the odd sizes in 3..blur_limit (or the given range)"""
+
+    def __init__(self, blur_limit=7, p=0.5, always_apply=False):
+        super().__init__(blur_limit, p, always_apply)
+
+    def get_params(self, g, H, W):
+        return self.ksize(g)
+
+    def taps(self, k):
+        return np.full(k, 1.0 / k, dtype=np.float32)
+
 
 class Compose:
     """albumentations ``Compose``: the transforms in order, each with its own probability; ``p`` gates the whole pipeline"""
@@ -290,7 +563,7 @@ class BatchAugment:
 
     def __call__(self, xb: torch.Tensor, yb: torch.Tensor):
         """augments xb [B, C, H, W] / yb [B, H, W] in place and returns them"""
-        if any(isinstance(t, _NEW_GEOMETRIC) for t in self.aug.transforms):
+        if any(isinstance(t, _NEW_GEOMETRIC) for t in self.aug.transforms) or (xb.is_cuda and not self.flips_only):
             return self._batched(xb, yb)
         B = xb.shape[0]
         n_transform = math.ceil(B * self.n)
@@ -299,7 +572,7 @@ class BatchAugment:
             xb[i], yb[i] = xi, yi
         return xb, yb
 
-    def draw(self, B: int, H: int, W: int) -> dict:
+    def draw(self, B: int, H: int, W: int, C=None) -> dict:
         """every random draw of ``__call__`` for a batch, image-major in the order of per-image ``Compose`` calls: {(image, transform
         index): parameters} for the transforms that fired"""
         fired = {}
@@ -308,7 +581,7 @@ class BatchAugment:
                 continue
             for k, t in enumerate(self.aug.transforms):
                 if self.g.random() < t.p:                # _Transform.__call__
-                    fired[i, k] = t.get_params(self.g, H, W)
+                    fired[i, k] = t.draw_params(self.g, C, H, W)
         return fired
 
     def segments(self) -> list:
@@ -334,21 +607,74 @@ class BatchAugment:
             interp |= t.interpolating
         return out
 
+    def plan(self) -> list:
+        """the launches of ``__call__`` in pipeline order: ("warp", [k, ...]) for a geometric segment (``segments``), ("pixel", [k, ...])
+        for a maximal run of pointwise transforms (one ``unet_pixel_ops`` launch over the batch), ("blur", k) for a separable filter
+        and ("image", k) for what runs image by image: RandomBrightnessContrast(brightness_by_max=False), which needs the mean of the
+        image, and transforms this module does not know"""
+        out = []
+        for seg in self.segments():
+            if not isinstance(seg, int):
+                out.append(("warp", seg))
+                continue
+            t = self.aug.transforms[seg]
+            if isinstance(t, _Blur):
+                out.append(("blur", seg))
+            elif isinstance(t, _Pointwise) and not (isinstance(t, RandomBrightnessContrast) and not t.by_max):
+                if out and out[-1][0] == "pixel" and out[-1][1][-1] == seg - 1:
+                    out[-1][1].append(seg)
+                else:
+                    out.append(("pixel", [seg]))
+            else:
+                out.append(("image", seg))
+        return out
+
+    def _pixel_run(self, x, y, run, fired):
+        """one launch for the pointwise transforms `run` of every image they fired for (and one per CoarseDropout that fills masks)"""
+        from . import ops
+        B, C, H, W = x.shape
+        ts = self.aug.transforms
+        progs = {i: [op for k in run if (i, k) in fired for op in ts[k].program(fired[i, k], C, H, W)] for i in range(B)}
+        if any(progs.values()):
+            ops.pixel_ops(x, progs)
+        for k in run:
+            rects = {i: ts[k].mask_rects(fired[i, k]) for i in range(B) if (i, k) in fired}
+            rects = {i: r for i, r in rects.items() if r is not None and r[0]}
+            if rects:
+                ops.fill_rects_mask(y, {i: r[0] for i, r in rects.items()}, next(iter(rects.values()))[1])
+
     def _batched(self, xb, yb):
-        B, H, W = xb.shape[0], xb.shape[-2], xb.shape[-1]
+        B, C, H, W = xb.shape
         ts = self.aug.transforms
         if H != W:
             for t in ts:
                 if isinstance(t, (RandomRotate90, Transpose)):
                     _square(type(t).__name__, H, W)
-        fired = self.draw(B, H, W)
+        for t in ts:
+            if isinstance(t, _Pointwise):
+                t.check(C, H, W)
+        fired = self.draw(B, H, W, C)
         x, y = xb, yb
-        for seg in self.segments():
-            if isinstance(seg, int):
-                t = ts[seg]
-                for i in range(B):
-                    if (i, seg) in fired:
-                        x[i], y[i] = t.apply_params(x[i], y[i], fired[i, seg])
+        for kind, seg in self.plan():
+            if kind == "pixel" and x.is_cuda:
+                if any((i, k) in fired for i in range(B) for k in seg):
+                    if not x.is_contiguous() or (y is not None and not y.is_contiguous()):
+                        x, y = x.contiguous(), y.contiguous()
+                    self._pixel_run(x, y, seg, fired)
+                continue
+            if kind == "blur" and x.is_cuda:
+                if any((i, seg) in fired for i in range(B)):
+                    from . import ops
+                    one = np.ones(1, dtype=np.float32)
+                    out = torch.empty_like(x, memory_format=torch.contiguous_format)
+                    ops.blur_separable(x.contiguous(), out, [ts[seg].taps(fired[i, seg]) if (i, seg) in fired else one for i in range(B)])
+                    x = out
+                continue
+            if kind != "warp":                            # image by image: a transform that needs the whole image, or a batch on the host
+                for k in (seg if kind == "pixel" else [seg]):
+                    for i in range(B):
+                        if (i, k) in fired:
+                            x[i], y[i] = ts[k].apply_params(x[i], y[i], fired[i, k])
                 continue
             if not any((i, k) in fired for i in range(B) for k in seg):
                 continue
@@ -363,6 +689,7 @@ class BatchAugment:
             x, y = _warp(x, y, maps, *lead.modes())
         if x is not xb:
             xb.copy_(x)
+        if y is not yb:
             yb.copy_(y)
         return xb, yb
 

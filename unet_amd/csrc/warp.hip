@@ -8,6 +8,7 @@
 // outside src / dst.  No atomics, no LDS: the result does not depend on launch order.
 #include <cmath>
 
+#include "border.h"
 #include "common.h"
 
 using namespace unet;
@@ -20,8 +21,6 @@ struct Maps {                 // passed by value in the kernel arguments (1.5 KB
     float m[MAXMAPS][6];
 };
 
-constexpr int B_CONSTANT = 0, B_REPLICATE = 1, B_REFLECT = 2, B_REFLECT101 = 4;      // cv2 border codes
-
 // source coordinates of the output pixel (x, y) under map m, clamped to +-2^24 (floor and the int conversion stay exact).  fp64: a
 // shifted, down-scaled map reaches coordinates of 10^4 - 10^5 pixels, where an fp32 coordinate is off by 10^-3 pixel and more; a few
 // fp64 FMAs per pixel cost nothing next to the memory traffic.
@@ -29,24 +28,6 @@ __device__ __forceinline__ void src_coords(const float* m, int x, int y, double&
     constexpr double LIM = 16777216.0;
     sx = fmin(fmax(fma((double)m[0], (double)x, fma((double)m[1], (double)y, (double)m[2])), -LIM), LIM);
     sy = fmin(fmax(fma((double)m[3], (double)x, fma((double)m[4], (double)y, (double)m[5])), -LIM), LIM);
-}
-
-// cv2.borderInterpolate for |i| <= 2^24 + 1 and N >= 1: an index in [0, N), or -1 (constant border: take the fill value)
-template <int BORDER>
-__device__ __forceinline__ int border_index(int i, int N) {
-    if (i >= 0 && i < N) return i;
-    if (BORDER == B_CONSTANT) return -1;
-    if (BORDER == B_REPLICATE) return i < 0 ? 0 : N - 1;
-    if (BORDER == B_REFLECT) {                         // fedcba|abcdef|fedcba: period 2N
-        const int P = 2 * N;
-        const int r = ((i % P) + P) % P;               // [0, 2N)
-        return r < N ? r : P - 1 - r;                  // [0, N)
-    }
-    // B_REFLECT101, gfedcb|abcdefg|fedcba: period 2N - 2
-    if (N == 1) return 0;
-    const int P = 2 * N - 2;
-    const int r = ((i % P) + P) % P;                   // [0, 2N - 2)
-    return r < N ? r : P - r;                          // [0, N)
 }
 
 // one tap of a plane: the value at offset o, or fill when the tap lies outside (constant border; o is 0 then).  The load is unconditional

@@ -987,6 +987,138 @@ def warp_affine_mask(src: torch.Tensor, dst: torch.Tensor, inv_maps, border: int
               "warp_affine_mask")
 
 
+# ------------------------------------------------------------------ pixel-level augmentation (csrc/pixel_aug.hip)
+
+def _pixel_pieces(what: str, ops_: list, Cc: int) -> list:
+    """one image's op list as programs the kernel takes: [(PixelOp list, rectangle list)], each <= 8 ops and <= 32 rectangles"""
+    flat = []
+    for op in ops_:
+        if op[0] == "rects":                                       # more than 32 rectangles: several FILL_RECTS ops
+            rects = list(op[1])
+            flat += [("rects", rects[k:k + L.PIXEL_MAX_RECTS], op[2]) for k in range(0, len(rects), L.PIXEL_MAX_RECTS)]
+        else:
+            flat.append(op)
+    pieces, cur, rects = [], [], []
+    for op in flat:
+        kind = op[0]
+        if len(cur) == L.PIXEL_MAX_OPS or (kind == "rects" and len(rects) + len(op[1]) > L.PIXEL_MAX_RECTS):
+            pieces.append((cur, rects))
+            cur, rects = [], []
+        if kind == "bc":
+            cur.append(L.PixelOp(L.PIXEL_BRIGHTNESS_CONTRAST, 0, 0, float(op[1]), float(op[2])))
+        elif kind == "gamma":
+            cur.append(L.PixelOp(L.PIXEL_GAMMA, 0, 0, float(op[1]), 0.0))
+        elif kind == "noise":
+            code = L.PIXEL_GAUSS_NOISE | (L.PIXEL_PER_CHANNEL if op[5] else 0)
+            cur.append(L.PixelOp(code, int(op[1]) & 0xffffffff, int(op[2]) & 0xffffffff, float(op[3]), float(op[4])))
+        elif kind == "rects":
+            cur.append(L.PixelOp(L.PIXEL_FILL_RECTS, len(rects), len(op[1]), float(op[2]), 0.0))
+            rects += [tuple(int(v) for v in r) for r in op[1]]
+        elif kind == "drop":
+            bits = 0
+            for c in op[1]:
+                if not 0 <= int(c) < Cc:
+                    raise ValueError(f"{what}: channel {c} of a {Cc}-channel image")
+                bits |= 1 << int(c)
+            cur.append(L.PixelOp(L.PIXEL_CHANNEL_DROP, bits, 0, float(op[2]), 0.0))
+        elif kind == "permute":
+            perm = [int(c) for c in op[1]]
+            if Cc > 16:
+                raise ValueError(f"{what}: a channel permutation supports at most 16 channels, the image has {Cc}")
+            if sorted(perm) != list(range(Cc)):
+                raise ValueError(f"{what}: {perm} is not a permutation of {Cc} channels")
+            bits = sum(c << (4 * k) for k, c in enumerate(perm))
+            cur.append(L.PixelOp(L.PIXEL_CHANNEL_PERMUTE, bits & 0xffffffff, bits >> 32, 0.0, 0.0))
+        else:
+            raise ValueError(f"{what}: unknown op {kind!r}")
+    if cur:
+        pieces.append((cur, rects))
+    return pieces
+
+
+def _fill_rects(dst, rects):
+    for k, r in enumerate(rects):
+        for q in range(4):
+            dst[k][q] = r[q]
+
+
+def pixel_ops(x: torch.Tensor, programs: dict):
+    """the pointwise programs {image index: [op, ...]} applied IN PLACE to the fp32 batch x [n, C, H, W] on the device, one launch per 8
+    images that have a program; images without one are not touched.  An op is ("bc", alpha, beta), ("gamma", gamma),
+    ("noise", key0, key1, mean, sigma, per_channel), ("rects", [(y0, x0, y1, x1), ...], fill), ("drop", [channel, ...], fill) or
+    ("permute", [source channel of channel 0, ...]): include/unet_hip.h."""
+    if not x.is_cuda:
+        raise RuntimeError(f"pixel_ops: the pixel programs run on the device only (HIP, no CPU fallback); got a {x.device} tensor")
+    assert x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32, (x.shape, x.dtype)
+    n, Cc, H, W = x.shape
+    pieces = {int(j): _pixel_pieces("pixel_ops", ops_, Cc) for j, ops_ in programs.items() if ops_}
+    assert all(0 <= j < n for j in pieces), (sorted(pieces), n)
+    for rnd in range(max((len(p) for p in pieces.values()), default=0)):        # (one round unless a program outgrows 8 ops / 32 rectangles)
+        todo = sorted(j for j, p in pieces.items() if len(p) > rnd)
+        for at in range(0, len(todo), L.PIXEL_MAX_PROGS):
+            chunk = todo[at:at + L.PIXEL_MAX_PROGS]
+            progs = (L.PixelProg * len(chunk))()
+            for pr, j in zip(progs, chunk):
+                ops_, rects = pieces[j][rnd]
+                pr.image, pr.nops, pr.nrects = j, len(ops_), len(rects)
+                for k, op in enumerate(ops_):
+                    pr.ops[k] = op
+                _fill_rects(pr.rects, rects)
+            check(lib.unet_pixel_ops(x.data_ptr(), n, Cc, H, W, C.addressof(progs), len(chunk), _stream()), "pixel_ops")
+
+
+def fill_rects_mask(mask: torch.Tensor, rects: dict, fill):
+    """the rectangles {mask index: [(y0, x0, y1, x1), ...]} of the device masks [n, H, W] (int64 or fp32) set to fill, in place"""
+    if not mask.is_cuda:
+        raise RuntimeError(f"fill_rects_mask: runs on the device only (HIP, no CPU fallback); got a {mask.device} tensor")
+    assert mask.dim() == 3 and mask.is_contiguous() and mask.dtype in (torch.int64, torch.float32), (mask.shape, mask.dtype)
+    n, H, W = mask.shape
+    todo = []                                                       # (mask index, at most 32 rectangles); an index may repeat
+    for j in sorted(rects):
+        assert 0 <= j < n, (j, n)
+        rs = [tuple(int(v) for v in r) for r in rects[j]]
+        todo += [(int(j), rs[k:k + L.PIXEL_MAX_RECTS]) for k in range(0, len(rs), L.PIXEL_MAX_RECTS)]
+    while todo:
+        chunk, rest, last = [], [], -1
+        for j, rs in todo:                                          # strictly increasing indices per launch
+            if len(chunk) < L.PIXEL_MAX_PROGS and j > last:
+                chunk.append((j, rs))
+                last = j
+            else:
+                rest.append((j, rs))
+        sets = (L.RectSet * len(chunk))()
+        for s, (j, rs) in zip(sets, chunk):
+            s.image, s.nrects = j, len(rs)
+            _fill_rects(s.rects, rs)
+        check(lib.unet_fill_rects_mask(mask.data_ptr(), int(mask.dtype == torch.float32), n, H, W, C.addressof(sets), len(chunk), float(fill),
+                                       _stream()), "fill_rects_mask")
+        todo = rest
+
+
+def blur_separable(src: torch.Tensor, dst: torch.Tensor, taps: list):
+    """dst[j] = src[j] filtered along rows and columns with taps[j] (an odd number of fp32 taps, at most 31; [1.0] copies), border
+    reflect-101; src / dst [n, C, H, W] fp32 on the device, out of place"""
+    if not (src.is_cuda and dst.is_cuda):
+        raise RuntimeError(f"blur_separable: the blur runs on the device only (HIP, no CPU fallback); got {src.device} / {dst.device} tensors")
+    assert src.dim() == 4 and src.is_contiguous() and dst.is_contiguous() and src.shape == dst.shape, (src.shape, dst.shape)
+    assert src.dtype == torch.float32 and dst.dtype == torch.float32, (src.dtype, dst.dtype)
+    import numpy as np
+    n, Cc, H, W = src.shape
+    assert len(taps) == n, (len(taps), n)
+    ks = np.array([len(t) for t in taps], dtype=np.int32)
+    if ks.max() > L.BLUR_MAX_KSIZE or not (ks % 2 == 1).all():
+        raise ValueError(f"blur_separable: kernel sizes {sorted(set(ks.tolist()))} (odd, at most {L.BLUR_MAX_KSIZE})")
+    tab = np.zeros((n, L.BLUR_MAX_KSIZE), dtype=np.float32)
+    for j, t in enumerate(taps):
+        tab[j, :len(t)] = t
+    per = Cc * H * W
+    for at in range(0, n, L.BLUR_MAX_IMAGES):
+        m = min(L.BLUR_MAX_IMAGES, n - at)
+        check(lib.unet_blur_separable(src.data_ptr() + at * per * 4, dst.data_ptr() + at * per * 4, m, Cc, H, W,
+                                      ks[at:at + m].ctypes.data_as(C.POINTER(C.c_int)), tab[at:at + m].ctypes.data_as(L.c_float_p), _stream()),
+              "blur_separable")
+
+
 def mosaic_accumulate_windows(z: TS, table: torch.Tensor, first: int, n: int, origin, mosaic: torch.Tensor, count: torch.Tensor,
                               row_lo: int, row_hi: int, raw: bool = False):
     """softmax (or, raw=True, the values themselves) of the fp32 NHWC logits of windows [first, first + n) added into mosaic / count"""
