@@ -73,7 +73,7 @@ __device__ __forceinline__ float fmul_unfused(float a, float b) {
 }  // namespace unet
 
 namespace unetconv {
-// the switches of a launch: the descriptor's struct or the defaults (read-only after load; env overrides: conv_igemm.hip)
+// the switches of a launch: the descriptor's struct or the defaults (read-only after load; env overrides: conv_dispatch.hip)
 const unet_tuning& tuning_defaults();
 static inline unet_tuning tuning_of(const unet_tuning* t) { return t != nullptr ? *t : tuning_defaults(); }
 }  // namespace unetconv

@@ -22,12 +22,6 @@ namespace {
 
 using namespace unetconv;
 
-constexpr int KCB = 32;   // reduction channels per chunk (64 bytes of bf16)
-// LDS halo row length in dwords: 64 bytes of channels + 32 bytes pad.  With 96-byte rows the 16 lanes of every ds_read_b128 lane group
-// ({0-3,12-15,20-27}, ...: pixel rows r, 16-byte slot (6 r + kq) mod 16) hit 16 different slots -- conflict free; the 80-byte rows of
-// the fp32 kernel are 2-way conflicted on 3 of 16 slots (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.5), which that MFMA-bound
-// kernel hides and this one (27 % MFMA busy) does not.
-constexpr int LDKB = 24;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -937,23 +931,34 @@ extern "C" int unet_debug_set_stamps(unsigned long long* buf) {
 
 template <int NTOT, int TW, typename T, bool SLV = false>
 int launch_t256n(const Plan& p, int y_f32, hipStream_t st) {
-    auto kern = conv_bf16_t256_kernel<NTOT, TW, T, SLV>;
-    static unsigned long long configured = 0;
-    if (unet::first_use_on_device(&configured))
-        UNET_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     // consecutive tiles per workgroup: as many as leave >= 4 workgroups for each of the 512 slots of the chip (2 per CU)
     const int ntiles = p.k.mtiles * p.k.ntn;
     int tpw = p.tune.t256_tiles_per_wg > 0 ? p.tune.t256_tiles_per_wg : ntiles / 2048;      // (unet_tuning.t256_tiles_per_wg forces a count)
     tpw = tpw < 1 ? 1 : (tpw > 16 ? 16 : tpw);
     dim3 grid = p.grid;
     grid.x = (unsigned)unet::roundup(unet::cdiv(ntiles, tpw), 8);
-    hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)2 * (256 / TW + 2) * (TW + 2) * T256_ROWB, st, p.k, y_f32, tpw, p.bn);
-    UNET_CHECK_LAUNCH();
-    return UNET_OK;
+    return launch_big_lds<conv_bf16_t256_kernel<NTOT, TW, T, SLV>>(grid, dim3(256), (size_t)2 * (256 / TW + 2) * (TW + 2) * T256_ROWB, st, p.k, y_f32, tpw, p.bn);
 }
 
-// the channel-tile count of a block is a template parameter: a launch whose last channel block is narrower than the others (Cout = 228 in
-// 128-wide blocks: 8 + 7 tiles) is issued as two launches over disjoint channel ranges
+// the channel-tile count of a block and the patch width are template parameters
+template <int TW, typename T>
+int launch_t256_tiles(const Plan& p, int tiles, int y_f32, hipStream_t st) {
+    switch (tiles) {
+        case 8: return launch_t256n<8, TW, T>(p, y_f32, st);
+        case 7: return launch_t256n<7, TW, T>(p, y_f32, st);
+        case 6: return launch_t256n<6, TW, T>(p, y_f32, st);
+        case 5: return launch_t256n<5, TW, T>(p, y_f32, st);
+        case 4: return launch_t256n<4, TW, T>(p, y_f32, st);
+        case 3: return launch_t256n<3, TW, T>(p, y_f32, st);
+        case 2: return launch_t256n<2, TW, T>(p, y_f32, st);
+        case 1: return launch_t256n<1, TW, T>(p, y_f32, st);
+    }
+    unet::set_error("conv: %d channel tiles in the 256-pixel tile", tiles);
+    return (int)UNET_E_UNSUPPORTED;
+}
+
+// a launch whose last channel block is narrower than the others (Cout = 228 in 128-wide blocks: 8 + 7 tiles) is issued as two launches over
+// disjoint channel ranges
 template <typename T>
 int launch_t256(const Plan& p, int y_f32, hipStream_t st) {
     const int cols = p.k.n_end - p.k.n_base, nblk = p.k.ntn, full = p.bn / 16;
@@ -964,30 +969,9 @@ int launch_t256(const Plan& p, int y_f32, hipStream_t st) {
             const int last_w = (q.k.n_end - q.k.n_base) - (q.k.ntn - 1) * q.bn - (tiles - 1) * 16;
             if (q.tune.t256_sliver && tiles == 7 && q.tw == 32 && last_w >= 1 && last_w <= 4) return launch_t256n<7, 32, T, true>(q, y_f32, st);
         }
-        if (q.tw == 32) {
-            switch (tiles) {
-                case 8: return launch_t256n<8, 32, T>(q, y_f32, st);
-                case 7: return launch_t256n<7, 32, T>(q, y_f32, st);
-                case 6: return launch_t256n<6, 32, T>(q, y_f32, st);
-                case 5: return launch_t256n<5, 32, T>(q, y_f32, st);
-                case 4: return launch_t256n<4, 32, T>(q, y_f32, st);
-                case 3: return launch_t256n<3, 32, T>(q, y_f32, st);
-                case 2: return launch_t256n<2, 32, T>(q, y_f32, st);
-                case 1: return launch_t256n<1, 32, T>(q, y_f32, st);
-            }
-        } else if (q.tw == 16) {
-            switch (tiles) {
-                case 8: return launch_t256n<8, 16, T>(q, y_f32, st);
-                case 7: return launch_t256n<7, 16, T>(q, y_f32, st);
-                case 6: return launch_t256n<6, 16, T>(q, y_f32, st);
-                case 5: return launch_t256n<5, 16, T>(q, y_f32, st);
-                case 4: return launch_t256n<4, 16, T>(q, y_f32, st);
-                case 3: return launch_t256n<3, 16, T>(q, y_f32, st);
-                case 2: return launch_t256n<2, 16, T>(q, y_f32, st);
-                case 1: return launch_t256n<1, 16, T>(q, y_f32, st);
-            }
-        }
-        unet::set_error("conv bf16: %d channel tiles / tile width %d in the 256-pixel tile", tiles, q.tw);
+        if (q.tw == 32) return launch_t256_tiles<32, T>(q, tiles, y_f32, st);
+        if (q.tw == 16) return launch_t256_tiles<16, T>(q, tiles, y_f32, st);
+        unet::set_error("conv: tile width %d in the 256-pixel tile", q.tw);
         return (int)UNET_E_UNSUPPORTED;
     };
     if (nblk == 1 || last_tiles == full) return one(p, nblk == 1 ? last_tiles : full);
@@ -1020,116 +1004,27 @@ __global__ void pack_weights_strided_bf16_kernel(const u16* __restrict__ w, long
     }
 }
 
-template <int TW, int MT, int NT, int WM, int WN, int HIT>
-int launch_cfg(const Plan& p, int y_f32, hipStream_t st) {
-    auto kern = conv_bf16_kernel<TW, MT, NT, WM, WN, HIT>;
-    static unsigned long long configured = 0;  // per instantiation, one bit per device
-    if (unet::first_use_on_device(&configured))
-        UNET_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(kern, p.grid, dim3(WM * WN * 64), p.lds_bytes, st, p.k, y_f32);
-    UNET_CHECK_LAUNCH();
-    return UNET_OK;
-}
-
-template <int TW, int HIT>
-int launch_bn(const Plan& p, int y_f32, hipStream_t st) {
-    if (p.bm == 256) {          // (dispatched to conv_bf16_t256_kernel by conv2d_bf16)
-        unet::set_error("conv bf16: inconsistent plan for the 256-pixel tile");
-        return UNET_E_UNSUPPORTED;
+// the generic bf16 tiles on the shared launch ladder (conv_common.h)
+struct IgemmBf16 {
+    template <int TW, int MT, int NT, int WM, int WN, int HIT>
+    static int launch(const Plan& p, int y_f32, hipStream_t st) {
+        return launch_big_lds<conv_bf16_kernel<TW, MT, NT, WM, WN, HIT>>(p.grid, dim3(WM * WN * 64), p.lds_bytes, st, p.k, y_f32);
     }
-    if constexpr (HIT == 6) {
-        unet::set_error("conv bf16: inconsistent plan (halo item count 6 without the 256-pixel tile)");
-        return UNET_E_UNSUPPORTED;
-    } else
-    if (p.bm == 64) {
-        if (p.bn == 64) return launch_cfg<TW, 1, 1, 2, 2, HIT>(p, y_f32, st);
-        return launch_cfg<TW, 1, 2, 2, 2, HIT>(p, y_f32, st);
-    }
-    switch (p.bn) {
-        case 32: return launch_cfg<TW, 1, 1, 4, 1, HIT>(p, y_f32, st);
-        case 64: return launch_cfg<TW, 2, 1, 2, 2, HIT>(p, y_f32, st);
-        default: return launch_cfg<TW, 2, 2, 2, 2, HIT>(p, y_f32, st);
-    }
-}
-
-template <int HIT>
-int launch_tw(const Plan& p, int y_f32, hipStream_t st) {
-    switch (p.tw) {
-        case 32: return launch_bn<32, HIT>(p, y_f32, st);
-        case 16: return launch_bn<16, HIT>(p, y_f32, st);
-        default: return launch_bn<8, HIT>(p, y_f32, st);
-    }
-}
-
-// splitk < 0: the tuning's own value; 0: a plan that must not split
-int plan_bf16(const unet_conv_desc* d, Plan* p, int splitk = -1) {
-    UNET_CHECK_ARG(d != nullptr, "conv: null desc");
-    const unet_tuning t = unetconv::tuning_of(d->tuning);
-    int rc = unetconv::make_plan(d, p, KCB, 8, 16, t.bf16_big_tile, splitk < 0 ? t.conv_splitk : splitk, t.plan_batch);
-    p->tune = t;
-    if (rc != UNET_OK) return rc;
-    UNET_CHECK_ARG(d->colsum == nullptr && d->colsumsq == nullptr, "conv bf16: column sums are not available in the bf16 kernel");
-    p->lds_bytes = (size_t)(32 + 2 * p->max_hpix * LDKB) * sizeof(float);
-    if (p->hit == 6) p->k.sliver = p->k.taps[0].dy[0] > 0 ? 1 : 0;      // 256-pixel tile: 1 = the taps of the input gradient (filter slabs backwards)
-    p->k.fold = (p->nparity == 1 && p->splits == 1 && bf16_fold_tail(d->Cin, d->ks * d->ks)) ? 1 : 0;
-    UNET_CHECK_ARG(d->Cout % 4 == 0 || d->y_co + unet::roundup(d->Cout, 4) <= d->y_cs, "conv bf16: the output slice must own its 4-channel padding");
-    UNET_CHECK_ARG(unet::aligned16(d->y) && (!d->res || unet::aligned16(d->res)) && (!d->mask || unet::aligned16(d->mask)),
-                   "conv bf16: y/res/mask must be 16-byte aligned");
-    return UNET_OK;
-}
+};
 
 }  // namespace
 
-namespace unetconv {
+int unetconv::conv_generic_bf16(const Plan& p, int y_f32, hipStream_t st) { return launch_generic<IgemmBf16>(p, y_f32, st); }
 
-// plan with split-K when the caller brought a workspace for it, else the plain plan
-static int plan_bf16_ws(const unet_conv_desc* d, Plan* p) {
-    int rc = plan_bf16(d, p);
-    if (rc != UNET_OK) return rc;
-    if (!splitk_redirect(d, p)) rc = plan_bf16(d, p, 0);
-    return rc;
-}
-
-int plan_bf16_public(const unet_conv_desc* d, Plan* p) { return plan_bf16(d, p); }
-
-int conv2d_bf16(const unet_conv_desc* d, hipStream_t st) {
-    Plan p;
-    int rc = plan_bf16_ws(d, &p);
-    if (rc != UNET_OK) return rc;
-    if (conv_smallk_applies(d)) return conv_smallk_bf16(d, st);
-    if (conv_smallcin_applies(d)) return conv_smallcin_bf16(d, st);
-    if (conv_head1x1_applies(d)) return conv_head1x1(d, st);
-    if (conv_gemm1x1_applies(d)) return conv_gemm1x1(d, st);
-    const int y_f32 = p.splits > 1 ? 1 : d->y_f32;        // partial sums are fp32 slabs
-    if (p.hit == 6) rc = launch_t256<unsigned short>(p, y_f32, st);
-    else rc = (p.hit == 10) ? launch_tw<10>(p, y_f32, st) : launch_tw<4>(p, y_f32, st);
-    if (rc != UNET_OK || p.splits <= 1) return rc;
-    return splitk_reduce(d, p, st);
-}
-
-// the fp32 launches the planner put on the 256-pixel tile (conv_igemm.hip: unet_conv2d)
-int conv2d_t256_f32(const Plan& p0, hipStream_t st) {
+// conv_bf16_t256_kernel reads two KArgs fields in a sense of its own: sliver = the taps of the input gradient (filter slabs backwards), fold =
+// the bf16 tap-folded tail (the float form has none)
+int unetconv::conv_t256(const Plan& p0, int dtype, int y_f32, hipStream_t st) {
     Plan p = p0;
-    p.k.sliver = p.k.taps[0].dy[0] > 0 ? 1 : 0;        // (this kernel reads the field as: the taps of the input gradient, filter slabs backwards)
+    p.k.sliver = p.k.taps[0].dy[0] > 0 ? 1 : 0;
+    if (dtype == UNET_BF16) return launch_t256<unsigned short>(p, y_f32, st);
     p.k.fold = 0;
     return launch_t256<float>(p, 1, st);
 }
-
-int conv2d_bf16_variant(const unet_conv_desc* d) {
-    Plan p;
-    int rc = plan_bf16_ws(d, &p);
-    if (rc != UNET_OK) return rc;
-    if (conv_smallk_applies(d)) return 9;          // conv1x1_smallk_kernel
-    if (conv_smallcin_applies(d)) return 10;       // conv3x3_smallcin_kernel
-    if (conv_head1x1_applies(d)) return 11;        // conv1x1_head_kernel
-    if (conv_gemm1x1_applies(d)) return 8;         // conv1x1_gemm_kernel
-    // 256-pixel tile: ...7 = the large layers (128-wide blocks, 32-pixel patches, >= 512 blocks: the launches bench.py's roofline follows), ...6 = its
-    // narrow-block / 16-pixel-patch / small-grid launches
-    const bool large = p.bm == 256 && p.bn == 128 && p.tw == 32 && (long long)p.k.mtiles * p.k.ntn >= 512;
-    return p.tw * 10000 + p.bn * 10 + (p.hit == 10 ? 1 : 0) + (p.bm == 64 ? 5 : 0) + (p.bm == 256 ? (large ? 7 : 6) : 0) + (p.splits > 1 ? 1000000 * p.splits : 0);
-}
-
-}  // namespace unetconv
 
 extern "C" size_t unet_pack_weights_size_bf16(int Cout, int Cin, int ks, int mode) {
     const int T = ks * ks;

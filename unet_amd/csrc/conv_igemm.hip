@@ -30,8 +30,6 @@ using namespace unetconv;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int KC = 16;   // reduction channels per chunk
-
 
 template <int HIT, int NTH>
 __device__ __forceinline__ void ld_halo(float4 (&hreg)[HIT], const int (&goff)[HIT], const float* xb, int c0, int Cin4, int tid) {
@@ -713,135 +711,22 @@ __global__ void pack_weights_strided_kernel(const float* __restrict__ w, long lo
 
 // ------------------------------------------------------------------ host side
 
-}  // namespace
-
-// The defaults of unet_tuning: constants, with environment overrides read ONCE when the library is loaded (A/B runs of whole programs).
-// Nothing writes them afterwards: the library has no mutable process state.
-namespace unetconv {
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return (e != nullptr && e[0] != 0) ? atoi(e) : dflt;
-}
-const unet_tuning& tuning_defaults() {
-    static const unet_tuning t = [] {
-        unet_tuning v;
-        v.conv_splitk = env_int("UNET_CONV_SPLITK", 1);
-        v.mfma_shape = 16;
-        v.f32_big_tile = 1;
-        v.bf16_big_tile = 1;
-        v.t256_tiles_per_wg = 0;
-        v.t256_sliver = env_int("UNET_T256_SLIVER", 1);
-        v.conv1x1_gemm = env_int("UNET_CONV1X1_GEMM", 0);
-        v.wgrad_mfma_shape = 32;
-        v.wgrad_bf16_k4 = 1;
-        v.wgrad_1x1 = 1;
-        v.wgrad_narrow = 1;
-        v.plan_batch = 0;
-        v.wgrad_wgs = env_int("UNET_WGRAD_WGS", 0);
-        v.conv_smallcin = env_int("UNET_CONV_SMALLCIN", 1);
-        v.conv_head1x1 = env_int("UNET_CONV_HEAD1X1", 1);
-        return v;
-    }();
-    return t;
-}
-}  // namespace unetconv
-
-extern "C" void unet_tuning_default(unet_tuning* t) {
-    if (t != nullptr) *t = unetconv::tuning_defaults();
-}
-
-namespace {
-
-// splitk < 0: the tuning's own value; 0: a plan that must not split (column-sum launches, a caller without a workspace)
-static int make_plan(const unet_conv_desc* d, Plan* p, int splitk = -1) {
-    UNET_CHECK_ARG(d != nullptr, "conv: null desc");
-    const unet_tuning t = unetconv::tuning_of(d->tuning);
-    UNET_CHECK_ARG(t.mfma_shape == 16 || t.mfma_shape == 32, "conv: unet_tuning.mfma_shape must be 16 or 32 (start from unet_tuning_default())");
-    const int rc = unetconv::make_plan(d, p, KC, 4, t.mfma_shape, t.f32_big_tile ? 1 : 0, splitk < 0 ? t.conv_splitk : splitk, t.plan_batch);
-    p->tune = t;
-    return rc;
-}
-
-
-template <int TW, int MT, int NT, int WM, int WN, int HIT>
-int launch_cfg(const Plan& p, hipStream_t st) {
-    if constexpr (MT == 2 && NT == 2 && WM == 2 && WN == 2 && HIT == 4) {
-        if (p.mf == 16 && p.k.sliver) {
-            auto kern = conv_igemm16_kernel<TW, MT, NT, WM, WN, HIT, true>;
-            static unsigned long long configured = 0;  // per instantiation, one bit per device
-            if (unet::first_use_on_device(&configured))
-                UNET_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            hipLaunchKernelGGL(kern, p.grid, dim3(WM * WN * 64), p.lds_bytes, st, p.k);
-            UNET_CHECK_LAUNCH();
-            return UNET_OK;
+// the generic fp32 tiles on the shared launch ladder (conv_common.h): the 16x16x4 kernel, its sliver form on the 128 x 128 tile, or the 32x32x2 kernel
+struct IgemmF32 {
+    template <int TW, int MT, int NT, int WM, int WN, int HIT>
+    static int launch(const Plan& p, int, hipStream_t st) {
+        const dim3 block(WM * WN * 64);
+        if constexpr (MT == 2 && NT == 2 && WM == 2 && WN == 2 && HIT == 4) {
+            if (p.mf == 16 && p.k.sliver) return launch_big_lds<conv_igemm16_kernel<TW, MT, NT, WM, WN, HIT, true>>(p.grid, block, p.lds_bytes, st, p.k);
         }
+        if (p.mf == 16) return launch_big_lds<conv_igemm16_kernel<TW, MT, NT, WM, WN, HIT>>(p.grid, block, p.lds_bytes, st, p.k);
+        return launch_big_lds<conv_igemm_kernel<TW, MT, NT, WM, WN, HIT>>(p.grid, block, p.lds_bytes, st, p.k);
     }
-    if (p.mf == 16) {
-        auto kern = conv_igemm16_kernel<TW, MT, NT, WM, WN, HIT>;
-        static unsigned long long configured = 0;  // per instantiation, one bit per device
-        if (unet::first_use_on_device(&configured))
-            UNET_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL(kern, p.grid, dim3(WM * WN * 64), p.lds_bytes, st, p.k);
-        UNET_CHECK_LAUNCH();
-        return UNET_OK;
-    }
-    auto kern = conv_igemm_kernel<TW, MT, NT, WM, WN, HIT>;
-    static unsigned long long configured = 0;  // per instantiation, one bit per device
-    if (unet::first_use_on_device(&configured))
-        UNET_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(kern, p.grid, dim3(WM * WN * 64), p.lds_bytes, st, p.k);
-    UNET_CHECK_LAUNCH();
-    return UNET_OK;
-}
-
-template <int TW, int HIT>
-int launch_bn(const Plan& p, hipStream_t st) {
-    if (p.bm == 64) {
-        if (p.bn == 64) return launch_cfg<TW, 1, 1, 2, 2, HIT>(p, st);
-        return launch_cfg<TW, 1, 2, 2, 2, HIT>(p, st);
-    }
-    switch (p.bn) {
-        case 32: return launch_cfg<TW, 1, 1, 4, 1, HIT>(p, st);
-        case 64: return launch_cfg<TW, 2, 1, 2, 2, HIT>(p, st);
-        default: return launch_cfg<TW, 2, 2, 2, 2, HIT>(p, st);
-    }
-}
-
-template <int HIT>
-int launch_tw(const Plan& p, hipStream_t st) {
-    switch (p.tw) {
-        case 32: return launch_bn<32, HIT>(p, st);
-        case 16: return launch_bn<16, HIT>(p, st);
-        default: return launch_bn<8, HIT>(p, st);
-    }
-}
+};
 
 }  // namespace
 
-extern "C" int unet_conv2d_colsum_rows(const unet_conv_desc* d) {
-    Plan p;
-    // the plan of the launch that WILL carry the column-sum pointers (they may still be null in this query): never split
-    int rc = make_plan(d, &p, 0);
-    if (rc != UNET_OK) return rc;
-    const int wm = (p.bn == 32 && p.bm == 128) ? 4 : 2;
-    return p.nparity * p.k.mtiles * wm;
-}
-
-static int make_plan_ws(const unet_conv_desc* d, Plan* p);
-
-extern "C" int unet_conv2d_variant(const unet_conv_desc* d) {
-    if (d != nullptr && d->pixel_shuffle) { const int rc = unetconv::conv_gemm1x1_ps_check(d); return rc == UNET_OK ? 8 : rc; }
-    if (d != nullptr && d->dtype == UNET_BF16) return unetconv::conv2d_bf16_variant(d);
-    Plan p;
-    int rc = make_plan_ws(d, &p);
-    if (rc != UNET_OK) return rc;
-    if (unetconv::conv_smallk_applies(d)) return 9;          // conv1x1_smallk_kernel
-    if (unetconv::conv_smallcin_applies(d)) return 10;       // conv3x3_smallcin_kernel
-    if (unetconv::conv_head1x1_applies(d)) return 11;        // conv1x1_head_kernel
-    if (unetconv::conv_gemm1x1_applies(d)) return 8;         // conv1x1_gemm_kernel
-    const bool large = p.bm == 256 && p.bn == 128 && p.tw == 32 && (long long)p.k.mtiles * p.k.ntn >= 512;
-    return p.tw * 10000 + p.bn * 10 + (p.hit == 10 ? 1 : 0) + (p.bm == 64 ? 5 : 0) + (p.bm == 256 ? (large ? 7 : 6) : 0) + (p.splits > 1 ? 1000000 * p.splits : 0);
-}
+int unetconv::conv_generic_f32(const Plan& p, hipStream_t st) { return launch_generic<IgemmF32>(p, 0, st); }
 
 // ------------------------------------------------------------------ split-K epilogue
 // y[p][c] = mask(act(sum_s slab[s][p][c] + bias[c] + res[p][c])): the slabs are added in split order (deterministic), four channels per
@@ -1007,8 +892,10 @@ __global__ __launch_bounds__(256) void conv1x1_smallk_kernel(const T* __restrict
     }
 }
 
+}  // namespace
+
 // the launches this kernel takes (both storage types; everything else about the descriptor was validated by the planner)
-bool smallk_applies(const unet_conv_desc* d) {
+bool unetconv::conv_smallk_applies(const unet_conv_desc* d) {
     const int vec = d->dtype == UNET_BF16 ? 8 : 4;
     return d->ks == 1 && d->stride == 1 && d->Cin <= 8 && d->Cout >= 16 && unet::roundup(d->Cout, vec) <= 512 && d->colsum == nullptr &&
            d->colsumsq == nullptr && d->cout_begin == 0 && (d->cout_count == 0 || d->cout_count == d->Cout) && d->wp_img_stride == 0 &&
@@ -1017,6 +904,7 @@ bool smallk_applies(const unet_conv_desc* d) {
            (!(d->flags & UNET_CONV_MASK) || unet::roundup(d->Cout, vec) <= d->mask_cs - d->mask_co);
 }
 
+namespace {
 template <typename T>
 int launch_smallk(const unet_conv_desc* d, hipStream_t st) {
     const long long P = (long long)d->N * d->OH * d->OW;
@@ -1159,16 +1047,19 @@ __global__ __launch_bounds__(256) void conv3x3_smallcin_kernel(const T* __restri
     }
 }
 
+}  // namespace
+
 // the launches it takes: a plain forward 3x3 conv (stride 1 | 2, padding 1) of <= 8 input channels held in ONE chunk of the packed image,
 // 16..32 output channels in whole vectors, no residual / mask / column sums / channel range.  Measured alone at 16 x 4 x 512^2 -> 32, stride 2
 // (scripts/ab_conv_smallcin.py): fp32 86 us against 271 us on conv_igemm16_kernel (bit-identical results: the same ascending (tap, channel)
 // chain of fused multiply-adds per output), bf16 93 against 180 us.  64 outputs lose to the MFMA kernels (8 -> 64: 273 / 219 us against
 // 150 / 55 us), and so does a single bf16 tile (17 against 13 us): bf16 launches below 2^18 output pixels stay where they were -- counted with
 // unet_tuning.plan_batch when that is set, so that a batch-invariant plan picks ONE kernel for every batch size.
-bool smallcin_applies(const unet_conv_desc* d) {
+bool unetconv::conv_smallcin_applies(const unet_conv_desc* d) {
+    const unet_tuning t = tuning_of(d->tuning);
     const int vec = d->dtype == UNET_BF16 ? 8 : 4;
-    const int plan_n = unetconv::tuning_of(d->tuning).plan_batch > 0 ? unetconv::tuning_of(d->tuning).plan_batch : d->N;
-    return d->ks == 3 && (d->stride == 1 || d->stride == 2) && d->kind == UNET_CONV_FWD && d->Cin <= 8 && d->Cout >= 16 && d->Cout <= 32 &&
+    const int plan_n = t.plan_batch > 0 ? t.plan_batch : d->N;
+    return t.conv_smallcin != 0 && d->ks == 3 && (d->stride == 1 || d->stride == 2) && d->kind == UNET_CONV_FWD && d->Cin <= 8 && d->Cout >= 16 && d->Cout <= 32 &&
            d->Cout % vec == 0 && d->res == nullptr && !(d->flags & UNET_CONV_MASK) && d->colsum == nullptr && d->colsumsq == nullptr &&
            d->cout_begin == 0 && (d->cout_count == 0 || d->cout_count == d->Cout) && d->wp_img_stride == 0 && !d->pixel_shuffle &&
            !(d->dtype == UNET_BF16 && d->y_f32) && d->Cout <= d->y_cs - d->y_co && unet::roundup(d->Cin, vec) <= d->x_cs - d->x_co &&
@@ -1176,6 +1067,7 @@ bool smallcin_applies(const unet_conv_desc* d) {
            (long long)d->N * d->OH * d->OW < (1ll << 31) - 256 * 12 * 1024 && (long long)d->IH * d->IW * d->x_cs < (1ll << 31);
 }
 
+namespace {
 template <typename T, int PX>
 int launch_smallcin_px(const unet_conv_desc* d, hipStream_t st) {
     const long long P = (long long)d->N * d->OH * d->OW;
@@ -1199,47 +1091,11 @@ int launch_smallcin(const unet_conv_desc* d, hipStream_t st) {
 }
 }  // namespace
 
-namespace unetconv {
-bool conv_smallk_applies(const unet_conv_desc* d) { return smallk_applies(d); }
-int conv_smallk_bf16(const unet_conv_desc* d, hipStream_t st) { return launch_smallk<unsigned short>(d, st); }
-bool conv_smallcin_applies(const unet_conv_desc* d) { return tuning_of(d->tuning).conv_smallcin != 0 && smallcin_applies(d); }
-int conv_smallcin_bf16(const unet_conv_desc* d, hipStream_t st) { return launch_smallcin<unsigned short>(d, st); }
+int unetconv::conv_smallk(const unet_conv_desc* d, hipStream_t st) {
+    return d->dtype == UNET_BF16 ? launch_smallk<unsigned short>(d, st) : launch_smallk<float>(d, st);
 }
-
-// plan with split-K when the caller brought a workspace for it, else the plain plan
-static int make_plan_ws(const unet_conv_desc* d, Plan* p) {
-    int rc = make_plan(d, p);
-    if (rc != UNET_OK) return rc;
-    if (!unetconv::splitk_redirect(d, p)) rc = make_plan(d, p, 0);
-    return rc;
-}
-
-extern "C" int unet_conv2d(const unet_conv_desc* d, void* stream) {
-    if (d != nullptr && d->pixel_shuffle) {          // 1x1 conv + activation + PixelShuffle(2) store: conv1x1_gemm_kernel only (both storage types)
-        const int rc = unetconv::conv_gemm1x1_ps_check(d);
-        return rc == UNET_OK ? unetconv::conv_gemm1x1(d, (hipStream_t)stream) : rc;
-    }
-    if (d != nullptr && d->dtype == UNET_BF16) return unetconv::conv2d_bf16(d, (hipStream_t)stream);
-    UNET_CHECK_ARG(d == nullptr || d->dtype == UNET_F32, "conv: unknown dtype %d", d->dtype);
-    Plan p;
-    int rc = make_plan_ws(d, &p);
-    if (rc != UNET_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (smallk_applies(d)) return launch_smallk<float>(d, st);
-    if (unetconv::conv_smallcin_applies(d)) return launch_smallcin<float>(d, st);
-    if (unetconv::conv_head1x1_applies(d)) return unetconv::conv_head1x1(d, st);
-    if (unetconv::conv_gemm1x1_applies(d)) return unetconv::conv_gemm1x1(d, st);
-    if (p.hit == 6) rc = unetconv::conv2d_t256_f32(p, st);          // the 256-pixel tile (conv_bf16.hip: conv_bf16_t256_kernel<.., float>)
-    else rc = (p.hit == 10) ? launch_tw<10>(p, st) : launch_tw<4>(p, st);
-    if (rc != UNET_OK || p.splits <= 1) return rc;
-    return unetconv::splitk_reduce(d, p, st);
-}
-
-extern "C" size_t unet_conv2d_splitk_workspace(const unet_conv_desc* d) {
-    Plan p;
-    if (d == nullptr || d->pixel_shuffle) return 0;
-    const int rc = d->dtype == UNET_BF16 ? unetconv::plan_bf16_public(d, &p) : make_plan(d, &p);
-    return rc == UNET_OK ? p.ws_floats : 0;
+int unetconv::conv_smallcin(const unet_conv_desc* d, hipStream_t st) {
+    return d->dtype == UNET_BF16 ? launch_smallcin<unsigned short>(d, st) : launch_smallcin<float>(d, st);
 }
 
 extern "C" size_t unet_pack_weights_size(int Cout, int Cin, int ks, int mode) {
