@@ -333,6 +333,21 @@ int unet_dice_fwd(const float* z, int z_cs, int z_co, const int64_t* target, int
                   long long mean_div, float* loss /*[1]*/, float* coef /*[B*C*2]*/, float* workspace, void* stream);
 int unet_dice_bwd(const float* z, int z_cs, int z_co, const int64_t* target, int B, long long HW, int C, int square_in_union,
                   const float* coef, float gscale, float* dz, int dz_cs, int dz_co, void* stream);
+/* CombinedLoss(axis=1, smooth, alpha, gamma, reduction, square_in_union, weight) = FocalLossFlat(gamma, weight) + alpha * DiceLoss(smooth,
+ * reduction, square_in_union), the compound loss fastai's documentation of DiceLoss ends with (gamma = 0: Dice + CE).  Both terms as defined
+ * above, in one pass over the logits per direction with one softmax per pixel.  unet_combined_fwd writes the terms SEPARATELY:
+ *   terms[0] = focal mean over all B * HW pixels,  terms[1] = Dice sum (divided by mean_div when mean_div > 0),
+ * and the Dice coefficients coef [B][C][2] exactly as unet_dice_fwd; the caller forms terms[0] + alpha * terms[1] (under tile-DDP after
+ * normalising each term in its own way).  unet_combined_bwd writes dz = fscale * d focal / d z + dscale * d dice / d z (fscale: loss scale /
+ * world, dscale: loss scale * alpha).  A target outside [0, C) adds 0 to the focal sum, counts in its mean and has no focal gradient; it
+ * is an all-zero one-hot row of the Dice term, whose gradient it keeps.  weight [C] or NULL feeds the focal term only.
+ * workspace = unet_combined_workspace(B, HW, C) floats.  C <= 64.  Deterministic (no atomics, fixed-order fp64 sums). */
+size_t unet_combined_workspace(int B, long long HW, int C);   /* floats */
+int unet_combined_fwd(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, int B, long long HW, int C, float gamma,
+                      float smooth, int square_in_union, long long mean_div, float* terms /*[2]*/, float* coef /*[B*C*2]*/, float* workspace,
+                      void* stream);
+int unet_combined_bwd(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, int B, long long HW, int C, float gamma,
+                      int square_in_union, const float* coef, float fscale, float dscale, float* dz, int dz_cs, int dz_co, void* stream);
 /* Regression mode (enable_regression, reference train.py:137-138,189-193; utils.py:145-147): n_out = 1, the loss is the mean over all
  * pixels of kind 0 = (z - t)^2 (MSELossFlat), 1 = |z - t| (L1LossFlat), 2 = SmoothL1(beta) (Smoothl1: beta 0.5).  z = channel z_co of
  * the NHWC output [P,z_cs], float targets [P]; workspace = unet_ce_workspace(P) floats.
@@ -549,6 +564,7 @@ int unet_copy_slice_bf16(const unet_bf16* x, int x_cs, int x_co, unet_bf16* y, i
 int unet_ce_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C, const float* denom, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
 int unet_focal_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C, float gamma, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
 int unet_dice_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, int B, long long HW, int C, int square_in_union, const float* coef, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
+int unet_combined_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, int B, long long HW, int C, float gamma, int square_in_union, const float* coef, float fscale, float dscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
 /* bf16 SelfAttention (round 3): the attention logits and the gradient of the attention weights stay fp32 (the products that make them write
  * fp32: unet_conv_desc.y_f32), the weights themselves and every other tensor are bf16 */
 int unet_pack_weights_strided_bf16(const unet_bf16* w, long long so, long long sr, unet_bf16* wp, int O, int R, void* stream);

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from unet_amd import xresnet34  # noqa: F401  (architecture tokens, like `from fastai.vision.all import xresnet34`)
-from unet_amd.learner import (Adam, CrossEntropyLossFlat, CSVLogger, DataLoaders, DiceLoss, DiceMulti, FlipAugment, FocalLossFlat, L1LossFlat, Learner,  # noqa: F401
+from unet_amd.learner import (Adam, CombinedLoss, CrossEntropyLossFlat, CSVLogger, DataLoaders, DiceLoss, DiceMulti, FlipAugment, FocalLossFlat, L1LossFlat, Learner,  # noqa: F401
                               Learner_adjust, MSELossFlat, R2Score, Rmse, SaveModelCallback, Smoothl1, TileDataset, load_learner,
                               open_tile)
 from unet_amd.model import HipDynamicUnet
@@ -94,8 +94,8 @@ def find_lr(learn, finder):
 def train_unet(class_weights, dls, architecture, epochs, path, lr, encoder_factor, lr_finder=None, regression=False,
                loss_func=None, monitor=None, existing_model=None, self_attention=False, export_model_summary=False) -> Learner:
     weights = torch.tensor(np.asarray(class_weights, dtype=np.float32), device=dls.device)
-    if regression and isinstance(loss_func, DiceLoss):
-        raise ValueError("DiceLoss is a classification loss: it cannot be used with regression=True")
+    if regression and isinstance(loss_func, (DiceLoss, CombinedLoss)):
+        raise ValueError(f"{type(loss_func).__name__} is a classification loss: it cannot be used with regression=True")
     if regression:                                                    # train.py:189-193
         if loss_func is None:
             loss_func = MSELossFlat(axis=1)

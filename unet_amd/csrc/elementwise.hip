@@ -1241,6 +1241,156 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
     }
 }
 
+// CombinedLoss(axis=1, smooth, alpha, gamma, reduction, square_in_union, weight) = FocalLossFlat(gamma, weight) + alpha * DiceLoss(smooth,
+// reduction, square_in_union): the compound of a pixel term and a region term (fastai's documentation of DiceLoss; gamma = 0 is the Dice + CE of
+// nnU-Net).  The two terms above, one pass over the logits per direction and one max / exp / sum per pixel for both.  Layout of the Dice
+// kernels (grid = B x bps, a block never straddles two samples); the logits are read once into registers, dice_softmax runs on that copy,
+// and the focal term takes max and sum from the same registers with the expressions of focal_fwd_kernel.  Block partials
+// [B][bps][I(C), U(C), F] (F = the block's sum of the focal values); one wavefront sums them in a fixed order in fp64 and writes the two
+// terms SEPARATELY -- terms[0] = focal mean over all B * HW pixels, terms[1] = Dice sum (divided by mean_div when > 0) -- with the Dice
+// coefficients [B][C][2] of dice_finalize_kernel: alpha and the N-rank normalisation, which differs between the terms, are the host's.
+// Backward: dz = fscale * d focal / dz + dscale * d dice / dz.  A target outside [0, C) has no focal gradient but keeps the Dice one.
+template <int CB>
+__device__ __forceinline__ float combined_ce(const float (&r)[CB], const float (&v)[CB], int C, long long y, float w) {
+    float m = r[0], s = 0.f, zy = 0.f;
+#pragma unroll
+    for (int c = 0; c < CB; ++c)
+        if (c < C) { m = fmaxf(m, r[c]); s += v[c]; zy = y == c ? r[c] : zy; }
+    return w * ((m + logf(s)) - zy);
+}
+
+template <int CB>
+__global__ __launch_bounds__(256) void combined_fwd_kernel(const float* __restrict__ z, int z_cs, int z_co, const int64_t* __restrict__ target,
+                                                           const float* __restrict__ weight, long long HW, int C, int bps, float gamma,
+                                                           int square, float* __restrict__ part) {
+    const int b = blockIdx.x / bps, k = blockIdx.x - b * bps;
+    float I[CB], U[CB], num = 0.f;
+#pragma unroll
+    for (int c = 0; c < CB; ++c) { I[c] = 0.f; U[c] = 0.f; }
+    const long long base = (long long)b * HW;
+    for (long long i = (long long)k * 256 + threadIdx.x; i < HW; i += (long long)bps * 256) {
+        const long long p = base + i;
+        const long long y = target[p];
+        const float* zp = z + (size_t)p * z_cs + z_co;
+        float r[CB], v[CB];
+#pragma unroll
+        for (int c = 0; c < CB; ++c)
+            if (c < C) r[c] = zp[c];
+        const float is = dice_softmax<CB>(r, C, v);
+#pragma unroll
+        for (int c = 0; c < CB; ++c) {
+            if (c >= C) continue;
+            const float pc = v[c] * is;
+            const bool hit = y == c;
+            I[c] += hit ? pc : 0.f;
+            U[c] += (square ? pc * pc : pc) + (hit ? 1.f : 0.f);
+        }
+        if (y >= 0 && y < C) {                        // ignore_index semantics of the focal term: 0 to the sum, still counted in the mean
+            float val, dval;
+            focal_terms(combined_ce<CB>(r, v, C, y, weight ? weight[y] : 1.f), gamma, val, dval);
+            num += val;
+        }
+    }
+    __shared__ float sI[4][CB], sU[4][CB], sF[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < CB; ++c) {
+        if (c >= C) continue;
+        float a = I[c], u = U[c];
+        for (int o = 32; o > 0; o >>= 1) {
+            a += __shfl_down(a, o);
+            u += __shfl_down(u, o);
+        }
+        if (lane == 0) { sI[wv][c] = a; sU[wv][c] = u; }
+    }
+    for (int o = 32; o > 0; o >>= 1) num += __shfl_down(num, o);
+    if (lane == 0) sF[wv] = num;
+    __syncthreads();
+    float* row = part + (size_t)blockIdx.x * (2 * C + 1);
+    for (int c = threadIdx.x; c < C; c += 256) {
+        row[c] = sI[0][c] + sI[1][c] + sI[2][c] + sI[3][c];
+        row[C + c] = sU[0][c] + sU[1][c] + sU[2][c] + sU[3][c];
+    }
+    if (threadIdx.x == 0) row[2 * C] = sF[0] + sF[1] + sF[2] + sF[3];
+}
+
+// one wavefront: the (b, c) pairs as in dice_finalize_kernel, then lane j sums the focal partials of the rows j, j + 64, ... in fp64
+__global__ __launch_bounds__(64) void combined_finalize_kernel(const float* __restrict__ part, int B, long long HW, int C, int bps, float smooth,
+                                                               long long mean_div, float* __restrict__ terms, float* __restrict__ coef) {
+    const double inv = mean_div > 0 ? 1.0 / (double)mean_div : 1.0, s = (double)smooth;
+    const size_t rs = (size_t)2 * C + 1;
+    double acc = 0.0, foc = 0.0;
+    for (int j = threadIdx.x; j < B * C; j += 64) {
+        const int b = j / C, c = j - b * C;
+        const float* q = part + (size_t)b * bps * rs + c;
+        double I = 0.0, U = 0.0;
+#pragma unroll 8
+        for (int r = 0; r < bps; ++r) {
+            I += (double)q[r * rs];
+            U += (double)q[r * rs + C];
+        }
+        const double num = 2.0 * I + s, den = U + s;
+        acc += 1.0 - num / den;
+        coef[2 * j] = (float)(-2.0 / den * inv);
+        coef[2 * j + 1] = (float)(num / (den * den) * inv);
+    }
+    for (int r = threadIdx.x; r < B * bps; r += 64) foc += (double)part[r * rs + 2 * C];
+    for (int o = 32; o > 0; o >>= 1) {
+        acc += __shfl_down(acc, o);
+        foc += __shfl_down(foc, o);
+    }
+    if (threadIdx.x == 0) {
+        terms[0] = (float)(foc / ((double)B * (double)HW));
+        terms[1] = (float)(acc * inv);
+    }
+}
+
+template <int CB, typename T>
+__global__ __launch_bounds__(256) void combined_bwd_kernel(const float* __restrict__ z, int z_cs, int z_co, const int64_t* __restrict__ target,
+                                                           const float* __restrict__ weight, long long HW, int C, int bps, float gamma,
+                                                           int square, const float* __restrict__ coef, float finv, float dscale,
+                                                           T* __restrict__ dz, int dz_cs, int dz_co) {
+    const int b = blockIdx.x / bps, k = blockIdx.x - b * bps;
+    __shared__ float sa[CB], sb[CB];
+    for (int c = threadIdx.x; c < C; c += 256) {
+        sa[c] = dscale * coef[2 * ((size_t)b * C + c)];
+        sb[c] = dscale * coef[2 * ((size_t)b * C + c) + 1];
+    }
+    __syncthreads();
+    const long long base = (long long)b * HW;
+    for (long long i = (long long)k * 256 + threadIdx.x; i < HW; i += (long long)bps * 256) {
+        const long long p = base + i;
+        const long long y = target[p];
+        const float* zp = z + (size_t)p * z_cs + z_co;
+        float r[CB], v[CB];
+#pragma unroll
+        for (int c = 0; c < CB; ++c)
+            if (c < C) r[c] = zp[c];
+        const float is = dice_softmax<CB>(r, C, v);
+        float g = 0.f;                                // focal: g (p_c - [c == y]), g = fscale / P * d focal / d ce * w[y]
+        if (y >= 0 && y < C) {
+            const float w = weight ? weight[y] : 1.f;
+            float val, dval;
+            focal_terms(combined_ce<CB>(r, v, C, y, w), gamma, val, dval);
+            g = dval * w * finv;
+        }
+        float dot = 0.f;
+#pragma unroll
+        for (int c = 0; c < CB; ++c) {
+            if (c >= C) continue;
+            v[c] *= is;
+            dot += v[c] * ((y == c ? sa[c] : 0.f) + sb[c] * (square ? 2.f * v[c] : 1.f));
+        }
+        T* dp = dz + (size_t)p * dz_cs + dz_co;
+#pragma unroll
+        for (int c = 0; c < CB; ++c) {
+            if (c >= C) continue;
+            const float dice = v[c] * ((y == c ? sa[c] : 0.f) + sb[c] * (square ? 2.f * v[c] : 1.f) - dot);
+            st1(dp + c, g * (v[c] - (y == c ? 1.f : 0.f)) + dice);
+        }
+    }
+}
+
 // Regression losses of the enable_regression branch (reference train.py:189-193: MSELossFlat(axis=1); utils.py:145-147:
 // Smoothl1 = SmoothL1Loss(beta=0.5); fastai L1LossFlat): prediction = channel 0 of the [P,1] output slice, float targets,
 // 'mean' reduction over all P pixels.  kind 0: d^2   1: |d|   2: |d| < beta ? d^2 / (2 beta) : |d| - beta / 2
@@ -1947,6 +2097,52 @@ extern "C" int unet_dice_bwd(const float* z, int z_cs, int z_co, const int64_t* 
                              const float* coef, float gscale, float* dz, int dz_cs, int dz_co, void* stream) { return dice_bwd_impl<float>(z, z_cs, z_co, target, B, HW, C, square_in_union, coef, gscale, dz, dz_cs, dz_co, stream); }
 extern "C" int unet_dice_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, int B, long long HW, int C, int square_in_union,
                              const float* coef, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream) { return dice_bwd_impl<unet_bf16>(z, z_cs, z_co, target, B, HW, C, square_in_union, coef, gscale, dz, dz_cs, dz_co, stream); }
+
+extern "C" size_t unet_combined_workspace(int B, long long HW, int C) {
+    if (B < 1 || HW < 1 || C < 1) return 0;
+    return (size_t)B * dice_bps(B, HW) * (2 * C + 1);
+}
+
+extern "C" int unet_combined_fwd(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, int B, long long HW, int C,
+                                 float gamma, float smooth, int square_in_union, long long mean_div, float* terms, float* coef,
+                                 float* workspace, void* stream) {
+    UNET_CHECK_ARG(z && target && terms && coef && workspace && B > 0 && HW > 0 && C > 0 && C <= CE_MAXC && gamma >= 0.f && mean_div >= 0,
+                   "combined_fwd: bad args");
+    UNET_CHECK_ARG(z_co >= 0 && z_co + C <= z_cs, "combined_fwd: bad slice");
+    const int bps = dice_bps(B, HW), sq = square_in_union ? 1 : 0;
+    const dim3 grid((unsigned)B * bps);
+    if (C <= 8) hipLaunchKernelGGL(combined_fwd_kernel<8>, grid, dim3(256), 0, ST, z, z_cs, z_co, target, weight, HW, C, bps, gamma, sq, workspace);
+    else if (C <= 16) hipLaunchKernelGGL(combined_fwd_kernel<16>, grid, dim3(256), 0, ST, z, z_cs, z_co, target, weight, HW, C, bps, gamma, sq, workspace);
+    else if (C <= 32) hipLaunchKernelGGL(combined_fwd_kernel<32>, grid, dim3(256), 0, ST, z, z_cs, z_co, target, weight, HW, C, bps, gamma, sq, workspace);
+    else hipLaunchKernelGGL(combined_fwd_kernel<64>, grid, dim3(256), 0, ST, z, z_cs, z_co, target, weight, HW, C, bps, gamma, sq, workspace);
+    UNET_CHECK_LAUNCH();
+    hipLaunchKernelGGL(combined_finalize_kernel, dim3(1), dim3(64), 0, ST, workspace, B, HW, C, bps, smooth, mean_div, terms, coef);
+    UNET_CHECK_LAUNCH();
+    return UNET_OK;
+}
+
+template <typename T>
+static int combined_bwd_impl(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, int B, long long HW, int C,
+                             float gamma, int square_in_union, const float* coef, float fscale, float dscale, T* dz, int dz_cs, int dz_co,
+                             void* stream) {
+    UNET_CHECK_ARG(z && target && coef && dz && B > 0 && HW > 0 && C > 0 && C <= CE_MAXC && gamma >= 0.f, "combined_bwd: bad args");
+    UNET_CHECK_ARG(z_co >= 0 && z_co + C <= z_cs && dz_co >= 0 && dz_co + C <= dz_cs, "combined_bwd: bad slice");
+    const int bps = dice_bps(B, HW), sq = square_in_union ? 1 : 0;
+    const float finv = fscale / (float)((long long)B * HW);       // the focal term is a mean over all pixels
+    const dim3 grid((unsigned)B * bps);
+    if (C <= 8) hipLaunchKernelGGL((combined_bwd_kernel<8, T>), grid, dim3(256), 0, ST, z, z_cs, z_co, target, weight, HW, C, bps, gamma, sq, coef, finv, dscale, dz, dz_cs, dz_co);
+    else if (C <= 16) hipLaunchKernelGGL((combined_bwd_kernel<16, T>), grid, dim3(256), 0, ST, z, z_cs, z_co, target, weight, HW, C, bps, gamma, sq, coef, finv, dscale, dz, dz_cs, dz_co);
+    else if (C <= 32) hipLaunchKernelGGL((combined_bwd_kernel<32, T>), grid, dim3(256), 0, ST, z, z_cs, z_co, target, weight, HW, C, bps, gamma, sq, coef, finv, dscale, dz, dz_cs, dz_co);
+    else hipLaunchKernelGGL((combined_bwd_kernel<64, T>), grid, dim3(256), 0, ST, z, z_cs, z_co, target, weight, HW, C, bps, gamma, sq, coef, finv, dscale, dz, dz_cs, dz_co);
+    UNET_CHECK_LAUNCH();
+    return UNET_OK;
+}
+extern "C" int unet_combined_bwd(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, int B, long long HW, int C,
+                                 float gamma, int square_in_union, const float* coef, float fscale, float dscale, float* dz, int dz_cs,
+                                 int dz_co, void* stream) { return combined_bwd_impl<float>(z, z_cs, z_co, target, weight, B, HW, C, gamma, square_in_union, coef, fscale, dscale, dz, dz_cs, dz_co, stream); }
+extern "C" int unet_combined_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, int B, long long HW, int C,
+                                 float gamma, int square_in_union, const float* coef, float fscale, float dscale, unet_bf16* dz, int dz_cs,
+                                 int dz_co, void* stream) { return combined_bwd_impl<unet_bf16>(z, z_cs, z_co, target, weight, B, HW, C, gamma, square_in_union, coef, fscale, dscale, dz, dz_cs, dz_co, stream); }
 
 extern "C" int unet_regloss_fwd(const float* z, int z_cs, int z_co, const float* target, long long P, int kind, float beta, float* loss,
                                 float* workspace, void* stream) {

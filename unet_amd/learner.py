@@ -8,7 +8,8 @@ train_bn, moms`` (``train.py:148-154``); ``unfreeze`` (``:246``); ``fit_one_cycl
 ``predict(item)`` -> 3-tuple whose [2] is per-class probabilities [C,H,W] (``predict.py:193-203``);
 ``get_preds``; ``summary``; callbacks ``SaveModelCallback(monitor, comp, fname)`` and ``CSVLogger`` (``train.py:209``);
 ``CrossEntropyLossFlat(axis=1, weight)`` with assignable ``.func.weight`` (``train.py:195,211``), ``FocalLossFlat(gamma, axis=1)``
-(``params_and_main.py:87-89``), ``DiceLoss(axis=1, smooth, reduction, square_in_union)``; ``DiceMulti``.
+(``params_and_main.py:87-89``), ``DiceLoss(axis=1, smooth, reduction, square_in_union)``, ``CombinedLoss(axis=1, smooth, alpha)`` (focal +
+alpha * Dice, from fastai's documentation of DiceLoss); ``DiceMulti``.
 """
 from __future__ import annotations
 
@@ -125,6 +126,51 @@ class DiceLoss:
         union = (p * p + t).sum(dims) if self.square_in_union else (p + t).sum(dims)
         loss = 1 - (2.0 * inter + self.smooth) / (union + self.smooth)
         return loss.mean() if self.reduction == "mean" else loss.sum()
+
+    def activation(self, x):
+        return torch.softmax(x, dim=self.axis)
+
+    def decodes(self, x):
+        return x.argmax(dim=self.axis)
+
+
+class CombinedLoss:
+    """The ``CombinedLoss`` fastai's documentation of DiceLoss ends with: ``focal(pred, targ) + alpha * dice(pred, targ)``, the compound of a
+    pixel term and a region term that segmentation of imbalanced classes is usually trained with (nnU-Net: Dice + CE, which is ``gamma=0``
+    here; MONAI: DiceCELoss / DiceFocalLoss).  The three positional arguments and their defaults are fastai's; the keyword-only ones expose
+    what fastai's version leaves at the inner losses' defaults.  ``focal`` is this module's ``FocalLossFlat(gamma, axis=1, weight)`` -- a
+    plain mean over all pixels, a target outside [0, C) adds 0 and still counts -- and ``dice`` its ``DiceLoss(axis, smooth, reduction,
+    square_in_union)``.  ``.func.weight`` (train.py:211 assigns it for every loss) feeds the focal term; the Dice term uses no class weights.
+    Fused on the device (unet_combined_fwd / unet_combined_bwd: one pass over the logits per direction for both terms).  At most 64 classes."""
+
+    def __init__(self, axis: int = 1, smooth: float = 1.0, alpha: float = 1.0, *, gamma: float = 2.0, reduction: str = "sum",
+                 square_in_union: bool = False, weight: Optional[torch.Tensor] = None):
+        assert axis == 1
+        if reduction not in ("sum", "mean"):
+            raise ValueError(f"CombinedLoss reduction must be 'sum' or 'mean', not {reduction!r}")
+        if not alpha >= 0:
+            raise ValueError(f"CombinedLoss alpha must be >= 0, not {alpha!r}")
+        if not gamma >= 0:
+            raise ValueError(f"CombinedLoss gamma must be >= 0, not {gamma!r}")
+        self.axis, self.smooth, self.alpha, self.gamma = axis, float(smooth), float(alpha), float(gamma)
+        self.reduction, self.square_in_union = reduction, bool(square_in_union)
+        self.func = _Func(weight)
+
+    _w = CrossEntropyLossFlat._w
+
+    def __call__(self, pred: torch.Tensor, targ: torch.Tensor) -> torch.Tensor:
+        """Generic path (torch autograd)."""
+        C = pred.shape[self.axis]
+        targ = targ.long()
+        valid = (targ >= 0) & (targ < C)
+        w = self._w(pred.device)
+        ce = torch.nn.functional.cross_entropy(pred, torch.where(valid, targ, -100), weight=None if w is None else w.to(pred.dtype),
+                                               reduction="none")
+        # an ignored pixel's ce is 0, where the derivative of (1 - exp(-ce)) ** gamma is unbounded for gamma < 1: keep it out of the power
+        ce = torch.where(valid, ce, 1.0)
+        focal = torch.where(valid, (1 - torch.exp(-ce)) ** self.gamma * ce, 0.0).mean()
+        dice = DiceLoss(self.axis, self.smooth, self.reduction, self.square_in_union)(pred, targ)
+        return focal + self.alpha * dice
 
     def activation(self, x):
         return torch.softmax(x, dim=self.axis)
@@ -695,7 +741,7 @@ class Learner:
         self.opt = self.opt_func(self.model, self.lr, wd_bn_bias=self.wd_bn_bias, splitter=self.splitter, **kw)
 
     def _weights(self):
-        return self.loss_func._w(self.dls.device) if isinstance(self.loss_func, CrossEntropyLossFlat) else None
+        return self.loss_func._w(self.dls.device) if isinstance(self.loss_func, (CrossEntropyLossFlat, CombinedLoss)) else None
 
     @property
     def _focal_gamma(self) -> Optional[float]:
@@ -704,6 +750,10 @@ class Learner:
     @property
     def _dice(self) -> Optional[DiceLoss]:
         return self.loss_func if isinstance(self.loss_func, DiceLoss) else None
+
+    @property
+    def _combined(self) -> Optional[CombinedLoss]:
+        return self.loss_func if isinstance(self.loss_func, CombinedLoss) else None
 
     @property
     def regression(self) -> bool:
@@ -736,18 +786,21 @@ class Learner:
         """batch_cb(it, loss_tensor, lr) -> True stops the fit after that batch (lr_find)."""
         model, opt = self.model, self.opt
         self._sync_replicas()
-        fused = isinstance(self.loss_func, (CrossEntropyLossFlat, _RegLoss, DiceLoss))
+        fused = isinstance(self.loss_func, (CrossEntropyLossFlat, _RegLoss, DiceLoss, CombinedLoss))
         if self.world > 1 and not fused:
-            raise RuntimeError("tile-DDP needs one of the fused losses (CrossEntropyLossFlat / FocalLossFlat / DiceLoss / MSELossFlat / L1LossFlat / "
-                               "Smoothl1)")
+            raise RuntimeError("tile-DDP needs one of the fused losses (CrossEntropyLossFlat / FocalLossFlat / DiceLoss / CombinedLoss / MSELossFlat / "
+                               "L1LossFlat / Smoothl1)")
         if self._dice is not None and model.n_out > ops.CE_MAXC:
             raise ValueError(f"DiceLoss supports at most {ops.CE_MAXC} classes, the model has {model.n_out}")
+        if self._combined is not None and model.n_out > ops.CE_MAXC:
+            raise ValueError(f"CombinedLoss supports at most {ops.CE_MAXC} classes, the model has {model.n_out}")
         step = TrainStep(model, opt, self._weights(), self.world) if fused else None
         if fused and self.regression:
             step.reg_kind, step.reg_beta = self.loss_func.kind, self.loss_func.beta
         if fused:
             step.focal_gamma = self._focal_gamma
             step.dice = self._dice
+            step.combined = self._combined
         n_iter = len(self.dls.train)
         total = max(1, n_epoch * n_iter)
         for cb in self.cbs:
@@ -820,6 +873,13 @@ class Learner:
                 ops.dice_fwd(z, yb, d.smooth, d.square_in_union, z.N * z.C if d.reduction == "mean" else 0, loss,
                              ctx.vec(self, "vcoef", 2 * z.N * z.C), ctx.workspace(ops.dice_workspace(z.N, z.H * z.W, z.C)))
                 acc[0] += loss[0].double() * z.N
+                acc[1] += z.N
+            elif self._combined is not None:           # like Dice: the batch loss weighted by the batch size
+                cl = self._combined
+                terms = ctx.vec(self, "vterms", 2)
+                ops.combined_fwd(z, yb, w, cl.gamma, cl.smooth, cl.square_in_union, z.N * z.C if cl.reduction == "mean" else 0, terms,
+                                 ctx.vec(self, "vcoef", 2 * z.N * z.C), ctx.workspace(ops.combined_workspace(z.N, z.H * z.W, z.C)))
+                acc[0] += (terms[0].double() + cl.alpha * terms[1].double()) * z.N
                 acc[1] += z.N
             elif self._focal_gamma is not None:          # a plain mean over the pixels: numerator = loss * P, denominator = P
                 ops.focal_fwd(z, yb, w, self._focal_gamma, loss, ctx.workspace(ops.ce_workspace(z.P)))
@@ -1023,6 +1083,7 @@ class Learner:
         """state dict + the constructor arguments (fastai pickles the whole Learner; that pickle needs fastai to load)."""
         m = self.model
         w = self.loss_func.func.weight if isinstance(self.loss_func, CrossEntropyLossFlat) else None
+        cl = self._combined
         meta = {"arch": m.arch, "n_in": m.n_in, "n_out": m.n_out, "img_size": list(m.img_size), "vocab": self.dls.vocab,
                 "dtype": self.dls.train_ds.dtype if self.dls is not None else "int8",
                 "class_weights": None if w is None else [float(v) for v in torch.as_tensor(w).cpu()],
@@ -1030,6 +1091,10 @@ class Learner:
                 "focal_gamma": self._focal_gamma,
                 **({"dice": {"smooth": self._dice.smooth, "reduction": self._dice.reduction, "square_in_union": self._dice.square_in_union}}
                    if self._dice is not None else {}),
+                **({"combined": {"smooth": cl.smooth, "alpha": cl.alpha, "gamma": cl.gamma, "reduction": cl.reduction,
+                                 "square_in_union": cl.square_in_union,
+                                 "class_weights": None if cl.func.weight is None else [float(v) for v in torch.as_tensor(cl.func.weight).cpu()]}}
+                   if cl is not None else {}),
                 "self_attention": bool(getattr(m, "self_attention", False)), "act_dtype": getattr(m, "act_dtype", "f32")}
         p = Path(fname)
         p = p if p.is_absolute() else self.path / p
@@ -1073,12 +1138,16 @@ def load_learner(fname, device="cuda", act_dtype: Optional[str] = None) -> Learn
 
 
 def _loss_from_meta(meta: dict):
-    """the loss object an exported file describes (Learner.export); files without a "dice" key load as they always have"""
+    """the loss object an exported file describes (Learner.export); files without a "dice" or a "combined" key load as they always have"""
     if meta.get("regression"):
         return {"mse": MSELossFlat, "l1": L1LossFlat, "smoothl1": Smoothl1}[meta["regression"]](axis=1)
     if meta.get("dice") is not None:
         d = meta["dice"]
         return DiceLoss(axis=1, smooth=d["smooth"], reduction=d["reduction"], square_in_union=d["square_in_union"])
+    if meta.get("combined") is not None:
+        d = meta["combined"]
+        return CombinedLoss(axis=1, smooth=d["smooth"], alpha=d["alpha"], gamma=d["gamma"], reduction=d["reduction"],
+                            square_in_union=d["square_in_union"], weight=None if d["class_weights"] is None else torch.tensor(d["class_weights"]))
     w = meta.get("class_weights")
     wt = None if w is None else torch.tensor(w)
     return CrossEntropyLossFlat(axis=1, weight=wt) if meta.get("focal_gamma") is None else FocalLossFlat(gamma=meta["focal_gamma"], axis=1, weight=wt)

@@ -465,7 +465,7 @@ class HipDynamicUnet(nn.Module):
 
     def forward_loss_backward(self, x: torch.Tensor, y: torch.Tensor, weight: Optional[torch.Tensor] = None,
                               grad_scale: float = 1.0, reg_kind: Optional[str] = None, reg_beta: float = 0.5,
-                              world: int = 1, focal_gamma: Optional[float] = None, dice=None) -> torch.Tensor:
+                              world: int = 1, focal_gamma: Optional[float] = None, dice=None, combined=None) -> torch.Tensor:
         """One fused training pass: logits -> loss -> backward into the flat gradient buffer.  Returns the loss as a 1-element
         device tensor (no host sync).  grad_scale multiplies the gradient.
         world > 1 (tile-DDP): the weighted cross-entropy is sum_r num_r / sum_r den_r over the ranks (den_r = sum of w[y] on
@@ -479,7 +479,20 @@ class HipDynamicUnet(nn.Module):
         dice: DiceLoss instead (params_and_main.py:16) -- any object with .smooth, .reduction ("sum" | "mean") and .square_in_union; class
         weights are not used.  Every (sample, class) term depends on one sample only: 'sum' needs no 1 / world pre-scale and the loss is
         SUM all-reduced; 'mean' divides by the global count of the terms (all-reduced with the loss, applied to the gradient coefficients).
+        combined: CombinedLoss instead -- any object with .gamma, .alpha, .smooth, .reduction and .square_in_union: focal(gamma, weight) +
+        alpha * dice in one loss kernel pair.  Each term keeps its own N-rank rule: ONE all-reduce of (focal, dice sum, count of the Dice
+        terms), the focal term averaged over the ranks and its gradient pre-scaled by 1 / world, the Dice term summed ('mean': divided by
+        the global count, as are its coefficients); alpha is applied on the device.
         Regression (reg_kind = "mse" | "l1" | "smoothl1", n_out = 1, float targets [B,H,W]): train.py:189-193."""
+        if combined is not None:
+            if dice is not None or focal_gamma is not None or reg_kind is not None:
+                raise ValueError("CombinedLoss is a loss of its own: it cannot be combined with dice=, focal_gamma= or a regression loss")
+            if self.n_out > ops.CE_MAXC:
+                raise ValueError(f"CombinedLoss supports at most {ops.CE_MAXC} classes, the model has {self.n_out}")
+            if combined.reduction not in ("sum", "mean"):
+                raise ValueError(f"CombinedLoss reduction must be 'sum' or 'mean', not {combined.reduction!r}")
+            if not (combined.alpha >= 0 and combined.gamma >= 0):
+                raise ValueError(f"CombinedLoss needs alpha >= 0 and gamma >= 0, not {combined.alpha!r} and {combined.gamma!r}")
         if dice is not None:
             if reg_kind is not None:
                 raise ValueError("DiceLoss is a classification loss: it cannot be combined with a regression loss")
@@ -492,7 +505,29 @@ class HipDynamicUnet(nn.Module):
         ctx = self.ctx
         P = z.P
         dz = ctx.act(self, "dlogits", z.N, z.H, z.W, z.C, zero=True)
-        if dice is not None:
+        if combined is not None:
+            cl = combined
+            y = y.to(self._device, torch.int64).contiguous()
+            loss, terms, coef = ctx.vec(self, "loss", 1), ctx.vec(self, "combined_terms", 3), ctx.vec(self, "dice_coef", 2 * z.N * z.C)
+            mean = cl.reduction == "mean"
+            ws = ctx.workspace(ops.combined_workspace(z.N, z.H * z.W, z.C))
+            fscale = grad_scale
+            if world > 1:
+                import torch.distributed as dist
+                # this rank's focal mean, its sum of the Dice terms and its count of them: one all-reduce, then each term's own rule
+                ops.combined_fwd(z, y, weight, cl.gamma, cl.smooth, cl.square_in_union, 0, terms, coef, ws)
+                terms[2].fill_(float(z.N * z.C))
+                dist.all_reduce(terms)
+                terms[0:1].div_(world)
+                if mean:
+                    terms[1:2].div_(terms[2:3])
+                    coef.div_(terms[2:3])
+                fscale = grad_scale / world
+            else:
+                ops.combined_fwd(z, y, weight, cl.gamma, cl.smooth, cl.square_in_union, z.N * z.C if mean else 0, terms, coef, ws)
+            torch.add(terms[0:1], terms[1:2], alpha=cl.alpha, out=loss)
+            ops.combined_bwd(z, y, weight, cl.gamma, cl.square_in_union, coef, fscale, grad_scale * cl.alpha, dz)
+        elif dice is not None:
             y = y.to(self._device, torch.int64).contiguous()
             loss, coef = ctx.vec(self, "loss", 1), ctx.vec(self, "dice_coef", 2 * z.N * z.C)
             mean = dice.reduction == "mean"

@@ -738,6 +738,33 @@ def dice_bwd(z: TS, target, square_in_union: bool, coef, gscale: float, dz: TS):
                               float(gscale), dz.ptr, dz.cs, dz.co, _stream()), "dice_bwd")
 
 
+def combined_workspace(B: int, HW: int, C: int) -> int:
+    return int(lib.unet_combined_workspace(B, HW, C))
+
+
+def combined_fwd(z: TS, target: torch.Tensor, weight, gamma: float, smooth: float, square_in_union: bool, mean_div: int, terms, coef, ws):
+    """CombinedLoss = focal + alpha * Dice in one pass over the logits: terms[0] = the FocalLossFlat(gamma, weight) mean over all pixels,
+    terms[1] = the DiceLoss(smooth, square_in_union) sum over the z.N samples and the classes, divided by mean_div when mean_div > 0; coef
+    [N*C*2] as dice_fwd writes it.  The caller combines the terms (alpha, tile-DDP normalisation)."""
+    _need_f32("combined_fwd", z)
+    if z.C > CE_MAXC:
+        raise ValueError(f"combined_fwd: at most {CE_MAXC} classes, got {z.C}")
+    HW = z.H * z.W
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == z.P and terms.numel() >= 2
+    assert coef.dtype == torch.float32 and coef.numel() >= 2 * z.N * z.C and ws.numel() >= combined_workspace(z.N, HW, z.C)
+    check(lib.unet_combined_fwd(z.ptr, z.cs, z.co, target.data_ptr(), _p(weight), z.N, HW, z.C, float(gamma), float(smooth),
+                                int(bool(square_in_union)), int(mean_div), terms.data_ptr(), coef.data_ptr(), ws.data_ptr(), _stream()),
+          "combined_fwd")
+
+
+def combined_bwd(z: TS, target, weight, gamma: float, square_in_union: bool, coef, fscale: float, dscale: float, dz: TS):
+    """dz = fscale * d focal / d z + dscale * d dice / d z (the terms of combined_fwd; dscale carries alpha)"""
+    assert dz.N == z.N and dz.H == z.H and dz.W == z.W and dz.C == z.C and coef.numel() >= 2 * z.N * z.C
+    check(_fn("combined_bwd", dz)(z.ptr, z.cs, z.co, target.data_ptr(), _p(weight), z.N, z.H * z.W, z.C, float(gamma),
+                                  int(bool(square_in_union)), coef.data_ptr(), float(fscale), float(dscale), dz.ptr, dz.cs, dz.co, _stream()),
+          "combined_bwd")
+
+
 REG_KINDS = {"mse": 0, "l1": 1, "smoothl1": 2}
 
 
