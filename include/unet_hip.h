@@ -492,6 +492,54 @@ int unet_warp_affine(const float* src, float* dst, int n, int C, int H, int W, c
 int unet_warp_affine_mask(const void* src, void* dst, int dst_f32, int n, int H, int W, const float* inv_maps_host, int border, double fill,
                           void* stream);
 
+/* -------------------------------------------------- non-rigid augmentation --
+ * The field augmentations of unet_amd.augment (albumentations ElasticTransform, GridDistortion, OpticalDistortion: cv2.remap per image on
+ * the host) on a device batch (csrc/warp_field.hip).  Output pixel p = (x, y) of image j takes the source value at pre_j * (p + d_j(p)):
+ * d_j is the displacement of the launch-wide kind, zero where images[j].fired == 0, and pre_j the 2 x 3 inverse map of the D4 transforms
+ * in front of the field transform (the identity 1 0 0 0 1 0 otherwise).  pre_j must be a D4 map of the H x W grid -- entries 0 / +-1,
+ * offsets 0 or N - 1, x and y swapped only when H == W; anything else is refused.  Sampling commutes with such a map, so the kernel
+ * applies it to the tap indices of p + d_j(p): bit for bit what permuting the image first and warping then gives.  images_host: n
+ * descriptors in host memory, read at call time and passed in the kernel arguments (n <= UNET_FIELD_MAX_IMAGES).
+ *   UNET_FIELD_DENSE    d = (field[j][0][y][x], field[j][1][y][x]); field [n, 2, H, W] fp32 on the device (not read for unfired images)
+ *   UNET_FIELD_GRID     p + d = (xx[x], yy[y]): an axis of N entries is cut into cells of grid_step entries (the last one clipped at N, at
+ *                       most UNET_FIELD_MAX_CELLS of them), and cell c runs from nodes[axis][c] to nodes[axis][c + 1] as
+ *                       np.linspace(prev, cur, len) does, endpoint included (a cell of one entry gets prev); axis 0 is x
+ *   UNET_FIELD_OPTICAL  with c = ((W - 1) / 2, (H - 1) / 2), u = (x - c_x) / W, v = (y - c_y) / H, r2 = u u + v v and k, dx, dy =
+ *                       optical[0..2]: p + d = (x + (x - c_x) k (r2 + r2 r2) + dx, y + (y - c_y) k (r2 + r2 r2) + dy), which is
+ *                       (W u kappa + c_x + dx, H v kappa + c_y + dy) for kappa = 1 + k r2 + k r2 r2
+ * Coordinates are evaluated in fp64 and clamped to +-2^24 (a NaN of the field becomes -2^24); interp, border, fill, the exact copy of a
+ * source on a grid point and the mask rule are those of unet_warp_affine / unet_warp_affine_mask.  Out of place.
+ * unet_elastic_field writes the dense field [n, 2, H, W] of ElasticTransform: plane q (0 = dx, 1 = dy; plane 0 twice with same_dxdy) at
+ * element e = y W + x starts as the noise 2 u - 1, u = ((w >> 8) + 0.5) 2^-24, w = word e % 4 of Philox4x32-10 under (key0, key1) at
+ * counter (e / 4, q, 0, 0); it is filtered along rows, then along columns with the ksize (odd, 1..UNET_ELASTIC_MAX_KSIZE) taps of
+ * taps_host, border reflect-101 repeated as often as the radius needs, and multiplied by alpha.  Unfired images get zeros.  workspace:
+ * n 2 H W floats for the row-pass result (contents on return unspecified).  n <= UNET_ELASTIC_MAX_IMAGES per call; the field of an
+ * image does not depend on the other images of the call.
+ * All return -1 before any launch on a null pointer, sizes or counts out of range, an unknown kind / interp / border, a non-finite
+ * parameter, a pre-map that is not a D4 map, or src == dst (field == dst, field == workspace). */
+#define UNET_FIELD_MAX_IMAGES 16
+#define UNET_FIELD_MAX_CELLS 16
+#define UNET_ELASTIC_MAX_IMAGES 64
+#define UNET_ELASTIC_MAX_KSIZE 401
+enum { UNET_FIELD_DENSE = 0, UNET_FIELD_GRID = 1, UNET_FIELD_OPTICAL = 2 };
+typedef struct unet_field_image {
+    int32_t fired;
+    float pre[6];
+    float optical[3];                                  /* k, dx, dy (pixels) */
+    float nodes[2][UNET_FIELD_MAX_CELLS + 1];          /* [0] x, [1] y */
+} unet_field_image;
+typedef struct unet_elastic_image {
+    uint32_t key0, key1;
+    float alpha;
+    int32_t fired, same_dxdy;
+} unet_elastic_image;
+int unet_warp_field(const float* src, float* dst, int n, int C, int H, int W, int kind, const unet_field_image* images_host,
+                    const float* field, int grid_step_x, int grid_step_y, int interp, int border, float fill, void* stream);
+int unet_warp_field_mask(const void* src, void* dst, int dst_f32, int n, int H, int W, int kind, const unet_field_image* images_host,
+                         const float* field, int grid_step_x, int grid_step_y, int border, double fill, void* stream);
+int unet_elastic_field(float* field, float* workspace, int n, int H, int W, const unet_elastic_image* images_host, const float* taps_host,
+                       int ksize, void* stream);
+
 /* -------------------------------------------------- pixel-level augmentation --
  * The radiometric augmentations of unet_amd.augment (albumentations RandomBrightnessContrast, CoarseDropout, RandomGamma, GaussNoise,
  * ChannelDropout, ChannelShuffle, GaussianBlur, Blur) on a device batch [n, C, H, W] fp32 (csrc/pixel_aug.hip).  Per-image parameters

@@ -5,7 +5,8 @@ Mirrors the reference's ``train.py`` surface: ``unet_learner_MS`` (``train.py:98
 with ``.tif`` (uncompressed GeoTIFF) or ``.npy`` tiles.  Regression mode (``enable_regression``: n_out = 1, MSELossFlat /
 L1LossFlat / Smoothl1, rmse + R2Score, ``Learner_adjust``) and the learning-rate finder (``LR_FINDER`` = valley / slide /
 steep / minimum, utils.py:150-167) are available.  ``aug_pipe`` takes a ``unet_amd.augment.Compose`` of the transforms that module
-has, with albumentations' signatures: flips, RandomRotate90, Transpose, Rotate, ShiftScaleRotate, RandomBrightnessContrast, CoarseDropout,
+has, with albumentations' signatures: flips, RandomRotate90, Transpose, Rotate, ShiftScaleRotate, ElasticTransform, GridDistortion,
+OpticalDistortion, RandomBrightnessContrast, CoarseDropout,
 RandomGamma, GaussNoise, GaussianBlur, Blur, ChannelDropout, ChannelShuffle.  Out of scope here: plots, albumentations
 itself and the transforms that module does not have, run-parameter JSON beyond a compact dump.
 """
@@ -157,6 +158,7 @@ def train_func(data_path, existing_model, model_Path, description, BATCH_SIZE, v
     if transforms:
         # aug_pipe: None = the reference's default pipeline HorizontalFlip + VerticalFlip (params_and_main.py:105-115); or a
         # unet_amd.augment.Compose (HorizontalFlip / VerticalFlip / RandomRotate90 / Transpose / Rotate / ShiftScaleRotate /
+        # ElasticTransform / GridDistortion / OpticalDistortion /
         # RandomBrightnessContrast / CoarseDropout / RandomGamma / GaussNoise / GaussianBlur / Blur / ChannelDropout / ChannelShuffle
         # with albumentations' semantics, applied on the device); a ready batch transform
         # (FlipAugment / BatchAugment) is used as is

@@ -103,6 +103,19 @@ class RectSet(C.Structure):
     _fields_ = [("image", C.c_uint32), ("nrects", C.c_uint32), ("rects", (C.c_uint16 * 4) * PIXEL_MAX_RECTS)]
 
 
+FIELD_MAX_IMAGES, FIELD_MAX_CELLS, ELASTIC_MAX_IMAGES, ELASTIC_MAX_KSIZE = 16, 16, 64, 401
+FIELD_DENSE, FIELD_GRID, FIELD_OPTICAL = 0, 1, 2
+
+
+class FieldImage(C.Structure):
+    """unet_field_image: the descriptor of one image of a field warp (include/unet_hip.h)"""
+    _fields_ = [("fired", C.c_int32), ("pre", C.c_float * 6), ("optical", C.c_float * 3), ("nodes", (C.c_float * (FIELD_MAX_CELLS + 1)) * 2)]
+
+
+class ElasticImage(C.Structure):
+    _fields_ = [("key0", C.c_uint32), ("key1", C.c_uint32), ("alpha", C.c_float), ("fired", C.c_int32), ("same_dxdy", C.c_int32)]
+
+
 class PackJob(C.Structure):
     _fields_ = [("w", vp), ("wp", vp), ("Cout", C.c_int), ("Cin", C.c_int), ("ks", C.c_int), ("mode", C.c_int), ("out_scale", vp)]
 
@@ -204,6 +217,9 @@ _sig = {
     "unet_dice_counts": (i, [vp, vp, ll, i, vp, vp]),
     "unet_warp_affine": (i, [vp, vp, i, i, i, i, c_float_p, i, i, f, vp]),
     "unet_warp_affine_mask": (i, [vp, vp, i, i, i, i, c_float_p, i, C.c_double, vp]),
+    "unet_warp_field": (i, [vp, vp, i, i, i, i, i, C.POINTER(FieldImage), vp, i, i, i, i, f, vp]),
+    "unet_warp_field_mask": (i, [vp, vp, i, i, i, i, i, C.POINTER(FieldImage), vp, i, i, i, C.c_double, vp]),
+    "unet_elastic_field": (i, [vp, vp, i, i, i, C.POINTER(ElasticImage), c_float_p, i, vp]),
     "unet_pixel_ops": (i, [vp, i, i, i, i, vp, i, vp]),
     "unet_fill_rects_mask": (i, [vp, i, i, i, i, vp, i, C.c_double, vp]),
     "unet_blur_separable": (i, [vp, vp, i, i, i, i, C.POINTER(C.c_int), c_float_p, vp]),

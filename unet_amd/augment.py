@@ -17,6 +17,13 @@ the transform's interpolation (0 nearest, 1 bilinear), masks always nearest (flo
 1 replicate, 2 reflect and 4 reflect-101.  Wrap borders, bicubic interpolation, ``crop_border=True`` and per-channel fill values are
 refused with NotImplementedError.
 
+Non-rigid transforms (``ElasticTransform``, ``GridDistortion``, ``OpticalDistortion``) are remaps on the device: output pixel p takes the
+source value at p + d(p) (``unet_warp_field`` / ``unet_warp_field_mask``, csrc/warp_field.hip), with the interpolation, border and fill
+rules of the affine warps.  The grid and optical displacements are evaluated per pixel from a few numbers per image; the elastic field is
+made on the device from two key words per image (``unet_elastic_field``: Philox noise smoothed by a separable Gaussian of up to 401 taps)
+and does not depend on how the batch is split into launches.  Their class docstrings state the maps in full and list what differs from
+albumentations; ``alpha_affine``, ``normalized=True`` and kernel sizes above 401 are refused with NotImplementedError.
+
 Pixel-level transforms (``RandomBrightnessContrast``, ``CoarseDropout``, ``RandomGamma``, ``GaussNoise``, ``ChannelDropout``,
 ``ChannelShuffle``) are pointwise: ``BatchAugment`` turns each maximal run of them into one short program per fired image and runs the
 programs of the whole batch in one launch (``unet_pixel_ops``, csrc/pixel_aug.hip).  ``GaussianBlur`` and ``Blur`` are one separable
@@ -202,7 +209,180 @@ class ShiftScaleRotate(_Warp):
         return m
 
 
-_NEW_GEOMETRIC = (RandomRotate90, Transpose, Rotate, ShiftScaleRotate)
+IDENTITY_MAP = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+class _Field(_Warp):
+    """a non-rigid warp: output pixel p takes the source value at p + d(p) (cv2.remap with the map p + d), through ``ops.warp_field`` /
+    ``ops.warp_field_mask`` (csrc/warp_field.hip).  ``kind`` names the kernel's displacement kind and ``field_params`` turns the drawn
+    parameters of a batch (None for an image that did not fire) into what the kernel takes for it.  A field transform closes its
+    geometric segment (``BatchAugment.segments``)."""
+    kind = ""
+
+    def field_params(self, prms: list, H: int, W: int, device):
+        raise NotImplementedError
+
+    def matrix(self, prm, H, W):
+        raise TypeError(f"{type(self).__name__} is not an affine map")
+
+    def warp_batch(self, img: torch.Tensor, mask, prms: list, pre_maps=None):
+        """image batch [n, C, H, W] and mask batch [n, H, W] (or None) sampled at pre_maps[j] * (p + d_j(p)) into new tensors; prms[j] is
+        None for an image that did not fire (d_j = 0)"""
+        from . import ops
+        H, W = img.shape[-2:]
+        fired = [prm is not None for prm in prms]
+        params = self.field_params(prms, H, W, img.device)
+        interp, border, fill, mask_fill = self.modes()
+        out = torch.empty_like(img, memory_format=torch.contiguous_format)
+        ops.warp_field(img.contiguous(), out, self.kind, params, fired, pre_maps, interp, border, fill)
+        if mask is None:
+            return out, None
+        mout = torch.empty_like(mask, memory_format=torch.contiguous_format)
+        ops.warp_field_mask(mask.contiguous(), mout, self.kind, params, fired, pre_maps, border, mask_fill)
+        return out, mout
+
+    def apply_params(self, img, mask, prm):
+        x, y = self.warp_batch(img[None], None if mask is None else mask[None], [prm])
+        return x[0], None if y is None else y[0]
+
+
+MAX_ELASTIC_KSIZE = 401
+
+
+def elastic_ksize(sigma: float, approximate: bool = False) -> int:
+    """the Gaussian kernel size of ElasticTransform: 17 when approximate, else cv2's rule for float images round(8 sigma + 1) | 1"""
+    return 17 if approximate else int(round(8.0 * float(sigma) + 1.0)) | 1
+
+
+def elastic_taps(sigma: float, ksize: int) -> np.ndarray:
+    """g[i] proportional to exp(-i^2 / (2 sigma^2)), i = -(ksize // 2) .. ksize // 2, normalised in fp64 and rounded to fp32"""
+    x = np.arange(ksize, dtype=np.float64) - (ksize - 1) * 0.5
+    t = np.exp(-(x * x) / (2.0 * float(sigma) ** 2))
+    return (t / t.sum()).astype(np.float32)
+
+
+class ElasticTransform(_Field):
+    """albumentations ``ElasticTransform(alpha=1, sigma=50, interpolation=1, border_mode=4, value=None, mask_value=None,
+    approximate=False, same_dxdy=False, alpha_affine=None, p)``, as this project defines it: two planes of uniform noise in (-1, 1), dx and
+    dy, are smoothed by a Gaussian of standard deviation ``sigma`` and multiplied by ``alpha``; output pixel (x, y) takes the source value
+    at (x + dx, y + dy).  The parameters are two Philox key words drawn from the seeded generator.  Noise plane q (0 = dx, 1 = dy) at
+    element e = y W + x is 2 u - 1, u = ((w >> 8) + 0.5) 2^-24, w = word e % 4 of Philox4x32-10 under the key at counter (e / 4, q, 0, 0):
+    the field is a pure function of the key and the pixel.  Each plane is filtered along rows, then along columns, with the taps
+    g[i] ~ exp(-i^2 / (2 sigma^2)) (``elastic_taps``: normalised in fp64, rounded to fp32) of a kernel of ``elastic_ksize`` entries --
+    round(8 sigma + 1) | 1, or 17 with ``approximate=True`` -- and border reflect-101, repeated as often as the radius needs.  With
+    ``same_dxdy`` dy is dx.
+
+    Known differences (albumentations and cv2 are not installed here, nothing was compared against them): albumentations draws the noise
+    from numpy's generator, so the fields differ draw by draw; the kernel-size rule is cv2's for float images as recalled, cv2 itself
+    may pick a smaller kernel for the same sigma; bilinear weights are fp32, without cv2's quantisation to 1/32 pixel.  A non-zero
+    ``alpha_affine`` (the random affine part of old releases) is refused: put a ``ShiftScaleRotate`` in front instead.  Kernel sizes
+    above 401 (sigma above 50 without ``approximate``) are refused."""
+    kind = "dense"
+
+    def __init__(self, alpha=1, sigma=50, interpolation=1, border_mode=4, value=None, mask_value=None, approximate=False, same_dxdy=False,
+                 alpha_affine=None, p=0.5, always_apply=False):
+        super().__init__(interpolation, border_mode, value, mask_value, p, always_apply)
+        if alpha_affine:
+            raise NotImplementedError(f"ElasticTransform: alpha_affine={alpha_affine!r} is not supported (only None or 0): put a "
+                                      "ShiftScaleRotate in front of it for the random affine part")
+        if not (float(sigma) > 0 and math.isfinite(float(sigma)) and math.isfinite(float(alpha))):
+            raise ValueError(f"ElasticTransform: alpha={alpha!r}, sigma={sigma!r} (finite, sigma > 0)")
+        self.alpha, self.sigma, self.same_dxdy = float(alpha), float(sigma), bool(same_dxdy)
+        self.ksize = elastic_ksize(sigma, approximate)
+        if self.ksize > MAX_ELASTIC_KSIZE:
+            raise NotImplementedError(f"ElasticTransform: sigma={sigma!r} needs a kernel of {self.ksize} taps, at most {MAX_ELASTIC_KSIZE} "
+                                      "are supported (sigma <= 50, or approximate=True)")
+        self.taps = elastic_taps(self.sigma, self.ksize)
+
+    def get_params(self, g, H, W):
+        return int(g.integers(0, 2 ** 32)), int(g.integers(0, 2 ** 32))
+
+    def field_params(self, prms, H, W, device):
+        from . import ops
+        field = torch.empty(len(prms), 2, H, W, dtype=torch.float32, device=device)
+        ops.elastic_field(field, torch.empty_like(field), [(0, 0) if prm is None else prm for prm in prms], self.alpha,
+                          [prm is not None for prm in prms], self.same_dxdy, self.taps)
+        return field
+
+
+MAX_GRID_CELLS = 16
+
+
+def grid_nodes(N: int, num_steps: int, factors) -> Tuple[int, np.ndarray]:
+    """(step, nodes) of one axis of GridDistortion: step = N // num_steps (at least 1) entries per cell and the node values 0 = nodes[0],
+    nodes[1], ... of albumentations' loop -- ``cur = prev + step * factors[i]``, or N where cell i was clipped at N -- as the 17 fp32
+    values the kernel takes (unused ones 0)"""
+    step = max(N // num_steps, 1)
+    cells = -(-N // step)
+    if cells > len(factors) or cells > MAX_GRID_CELLS:
+        raise ValueError(f"GridDistortion: {N} pixels in steps of {step} are {cells} cells, more than the {len(factors)} factors of "
+                         f"num_steps={num_steps} (albumentations fails on this as well)")
+    nodes, prev = np.zeros(MAX_GRID_CELLS + 1, dtype=np.float64), 0.0
+    for i in range(cells):
+        prev = float(N) if i * step + step > N else prev + step * float(factors[i])
+        nodes[i + 1] = prev
+    return step, nodes.astype(np.float32)
+
+
+class GridDistortion(_Field):
+    """albumentations ``GridDistortion(num_steps=5, distort_limit=0.3, interpolation=1, border_mode=4, value=None, mask_value=None,
+    normalized=False, p)``: num_steps + 1 factors 1 + U(distort_limit) per axis (x first); the source column table xx is albumentations'
+    loop -- step = W // num_steps, cell i covers [i step, min(i step + step, W)), ``cur = prev + step * f_i`` (W where the cell was
+    clipped) and the cell is filled with ``np.linspace(prev, cur, len)``, endpoint included, so a cell of one pixel gets prev -- rows the
+    same with H; output pixel (x, y) takes the source value at (xx[x], yy[y]).  The node values prev / cur go to the kernel as fp32.
+
+    Known differences (nothing was compared against the package): a tile narrower than num_steps uses step 1, where albumentations
+    divides by a zero step; ``normalized=True`` is refused, and so is a ``num_steps`` outside 1..15 (16 cells per axis)."""
+    kind = "grid"
+
+    def __init__(self, num_steps=5, distort_limit=0.3, interpolation=1, border_mode=4, value=None, mask_value=None, normalized=False, p=0.5,
+                 always_apply=False):
+        super().__init__(interpolation, border_mode, value, mask_value, p, always_apply)
+        if normalized:
+            raise NotImplementedError("GridDistortion: normalized=True is not supported")
+        if not 1 <= int(num_steps) <= MAX_GRID_CELLS - 1 or int(num_steps) != num_steps:
+            raise NotImplementedError(f"GridDistortion: num_steps={num_steps!r} is not supported (1..{MAX_GRID_CELLS - 1})")
+        self.num_steps, self.limit = int(num_steps), _limit(distort_limit)
+
+    def get_params(self, g, H, W):
+        fx = [1.0 + float(g.uniform(*self.limit)) for _ in range(self.num_steps + 1)]
+        fy = [1.0 + float(g.uniform(*self.limit)) for _ in range(self.num_steps + 1)]
+        return fx, fy
+
+    def field_params(self, prms, H, W, device):
+        nodes = np.zeros((len(prms), 2, MAX_GRID_CELLS + 1), dtype=np.float32)
+        step_x, step_y = max(W // self.num_steps, 1), max(H // self.num_steps, 1)
+        for j, prm in enumerate(prms):
+            if prm is not None:
+                nodes[j, 0], nodes[j, 1] = grid_nodes(W, self.num_steps, prm[0])[1], grid_nodes(H, self.num_steps, prm[1])[1]
+        return step_x, step_y, nodes
+
+
+class OpticalDistortion(_Field):
+    """albumentations ``OpticalDistortion(distort_limit=0.05, shift_limit=0.05, interpolation=1, border_mode=4, value=None,
+    mask_value=None, p)``, as this project defines it: k = U(distort_limit), dx = U(shift_limit) W, dy = U(shift_limit) H; with
+    c = ((W - 1) / 2, (H - 1) / 2), u' = (x - c_x) / W, v' = (y - c_y) / H, r^2 = u'^2 + v'^2 and kappa = 1 + k r^2 + k r^4, output pixel
+    (x, y) takes the source value at (W u' kappa + c_x + dx, H v' kappa + c_y + dy): the identity at k = 0, dx = dy = 0.
+
+    Known differences (nothing was compared against the package): cv2's own map (initUndistortRectifyMap with focal lengths W, H), as
+    far as recalled, places the projection centre at (W / 2, H / 2) and so shifts by half a pixel; albumentations 1.3 rounds the shift
+    to whole pixels."""
+    kind = "optical"
+
+    def __init__(self, distort_limit=0.05, shift_limit=0.05, interpolation=1, border_mode=4, value=None, mask_value=None, p=0.5,
+                 always_apply=False):
+        super().__init__(interpolation, border_mode, value, mask_value, p, always_apply)
+        self.distort, self.shift = _limit(distort_limit), _limit(shift_limit)
+
+    def get_params(self, g, H, W):
+        k = float(g.uniform(*self.distort))
+        return k, float(g.uniform(*self.shift)) * W, float(g.uniform(*self.shift)) * H
+
+    def field_params(self, prms, H, W, device):
+        return np.array([(0.0, 0.0, 0.0) if prm is None else prm for prm in prms], dtype=np.float32).reshape(len(prms), 3)
+
+
+_NEW_GEOMETRIC = (RandomRotate90, Transpose, Rotate, ShiftScaleRotate, ElasticTransform, GridDistortion, OpticalDistortion)
 
 
 def inverse_map(forward: np.ndarray) -> np.ndarray:
@@ -587,24 +767,31 @@ class BatchAugment:
     def segments(self) -> list:
         """the pipeline in execution order: a list of transform indices for each geometric segment (one warp launch over the batch), an
         int for each other transform (run per image).  A segment is a maximal run of geometric transforms with at most one
-        interpolating transform.
+        interpolating transform.  A field transform (ElasticTransform, GridDistortion, OpticalDistortion) closes its segment, and only D4
+        transforms may stand in front of it there: the next geometric transform starts a new segment.
 
         Composing inside a segment equals applying its transforms one after another: a D4 map (flip, transpose, multiple of 90 degrees)
         permutes the grid exactly, and on a square grid bilinear interpolation and the four border modes commute with it -- the
         bilinear weights and the constant / replicate / reflect / reflect-101 extensions are symmetric under the D4 symmetries of the
         image square.  Sampling a D4-permuted image at q is sampling the image at the permuted q, and permuting a warped image permutes
-        its sample points.  Two interpolations in a row are not one interpolation of the composed map, hence one per segment."""
-        out, seg, interp = [], None, False
+        its sample points.  Two interpolations in a row are not one interpolation of the composed map, hence one per segment.
+
+        The same argument covers D4 transforms in front of a field transform: with Minv the inverse of the composed D4 maps that fired
+        for an image, the field transform samples the permuted image at p + d(p), which is the image itself at Minv (p + d(p)) -- one
+        launch that applies Minv to the displaced point.  A transform BEHIND a field transform would have to permute the displacement
+        field as well, hence the closed segment."""
+        out, seg, interp, closed = [], None, False, False
         for k, t in enumerate(self.aug.transforms):
             if not isinstance(t, _Geometric):
                 out.append(k)
                 seg = None
                 continue
-            if seg is None or (t.interpolating and interp):
+            if seg is None or closed or (t.interpolating and interp):
                 seg, interp = [], False
                 out.append(seg)
             seg.append(k)
             interp |= t.interpolating
+            closed = isinstance(t, _Field)
         return out
 
     def plan(self) -> list:
@@ -678,13 +865,17 @@ class BatchAugment:
                 continue
             if not any((i, k) in fired for i in range(B) for k in seg):
                 continue
+            last = ts[seg[-1]]
             maps = np.empty((B, 6), dtype=np.float32)
             for i in range(B):
                 fwd = np.eye(3)
-                for k in seg:
+                for k in (seg[:-1] if isinstance(last, _Field) else seg):
                     if (i, k) in fired:
                         fwd = ts[k].matrix(fired[i, k], H, W) @ fwd
                 maps[i] = inverse_map(fwd)
+            if isinstance(last, _Field):               # the D4 maps of the segment go in as the pre-map of the field warp
+                x, y = last.warp_batch(x, y, [fired.get((i, seg[-1])) for i in range(B)], maps)
+                continue
             lead = next((ts[k] for k in seg if ts[k].interpolating), ts[seg[0]])
             x, y = _warp(x, y, maps, *lead.modes())
         if x is not xb:

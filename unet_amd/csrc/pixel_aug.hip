@@ -20,6 +20,7 @@
 
 #include "border.h"
 #include "common.h"
+#include "philox.h"
 
 using namespace unet;
 
@@ -37,23 +38,6 @@ struct Taps {                 // 2 KB
     int k[UNET_BLUR_MAX_IMAGES];
     float t[UNET_BLUR_MAX_IMAGES][UNET_BLUR_MAX_KSIZE];
 };
-
-// ---------------------------------------------------------------------------------------------------------------- Philox4x32-10
-__device__ __forceinline__ void philox4x32_10(uint32_t q, uint32_t k0, uint32_t k1, uint32_t w[4]) {
-    uint32_t c0 = q, c1 = 0, c2 = 0, c3 = 0;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
-}
 
 // The Box-Muller pair of words (w0, w1): r cos(2 pi u1), r sin(2 pi u1), r = sqrt(-2 ln u0), u = ((w >> 8) + 0.5) 2^-24.  u has 25
 // significant bits, one more than fp32 holds, so both functions get an argument that IS exact: ln u0 as log1p(-(1 - u0)) in the upper
@@ -99,7 +83,7 @@ __device__ __forceinline__ void apply_ops(const unet_pixel_prog& pr, const Px<V>
                 const uint32_t plane = (op.code & UNET_PIXEL_PER_CHANNEL) ? c : 0u;
                 const uint32_t e = (plane * (uint32_t)H + (uint32_t)px.y) * (uint32_t)W + (uint32_t)px.x;
                 uint32_t w[4];
-                philox4x32_10(e >> 2, op.u0, op.u1, w);
+                philox4x32_10(e >> 2, 0u, op.u0, op.u1, w);
                 float z[4];
                 if (V == 4) {                                        // W % 4 == 0 and x % 4 == 0: the four pixels are one counter
                     box_muller(w[0], w[1], z[0], z[1]);

@@ -1014,6 +1014,111 @@ def warp_affine_mask(src: torch.Tensor, dst: torch.Tensor, inv_maps, border: int
               "warp_affine_mask")
 
 
+# ------------------------------------------------------------------ non-rigid augmentation (csrc/warp_field.hip)
+
+FIELD_KINDS = {"dense": L.FIELD_DENSE, "grid": L.FIELD_GRID, "optical": L.FIELD_OPTICAL}
+
+
+def _field_args(what: str, src: torch.Tensor, dst: torch.Tensor, kind: str, params, fired, pre_maps, dims: int):
+    """the checked arguments of a field warp: (kind code, descriptor array, field tensor or None, grid steps)"""
+    import numpy as np
+    if kind not in FIELD_KINDS:
+        raise ValueError(f"{what}: unknown kind {kind!r} (dense, grid, optical)")
+    n = src.shape[0]
+    pre = np.tile(np.array([1, 0, 0, 0, 1, 0], np.float32), (n, 1)) if pre_maps is None else pre_maps
+    pre = _warp_args(what, src, dst, pre, dims)
+    flags = [bool(v) for v in fired]
+    assert len(flags) == n, (what, len(flags), n)
+    H, W = src.shape[-2:]
+    images = (L.FieldImage * n)()
+    for j in range(n):
+        images[j].fired = int(flags[j])
+        images[j].pre[:] = pre[j].tolist()
+    field, steps = None, (0, 0)
+    if kind == "dense":
+        field = params
+        if not field.is_cuda:
+            raise RuntimeError(f"{what}: the field lives on the device (HIP, no CPU fallback); got a {field.device} tensor")
+        assert field.dtype == torch.float32 and field.is_contiguous() and tuple(field.shape) == (n, 2, H, W), (what, field.shape, field.dtype)
+    elif kind == "grid":
+        step_x, step_y, nodes = params
+        nodes = np.ascontiguousarray(nodes, dtype=np.float32)
+        steps = (int(step_x), int(step_y))
+        assert nodes.shape == (n, 2, L.FIELD_MAX_CELLS + 1), (what, nodes.shape)
+        if min(steps) < 1 or -(-W // steps[0]) > L.FIELD_MAX_CELLS or -(-H // steps[1]) > L.FIELD_MAX_CELLS:
+            raise ValueError(f"{what}: grid steps {steps} on a {H} x {W} image (1..{L.FIELD_MAX_CELLS} cells per axis)")
+        for j in range(n):
+            for a in range(2):
+                images[j].nodes[a][:] = nodes[j, a].tolist()
+    else:
+        opt = np.ascontiguousarray(params, dtype=np.float32)
+        assert opt.shape == (n, 3), (what, opt.shape)
+        for j in range(n):
+            images[j].optical[:] = opt[j].tolist()
+    return FIELD_KINDS[kind], images, field, steps
+
+
+def warp_field(src: torch.Tensor, dst: torch.Tensor, kind: str, params, fired, pre_maps=None, interp: int = 1, border: int = 4,
+               fill: float = 0.0):
+    """dst[j] = src[j] sampled at pre_maps[j] * (p + d_j(p)) (include/unet_hip.h): kind "dense" with params the field [n, 2, H, W] fp32
+    on the device, "grid" with params (step_x, step_y, nodes [n, 2, 17]) or "optical" with params [n, 3] = (k, dx, dy); d_j = 0 where
+    fired[j] is false; pre_maps [n, 6]: D4 maps of the grid as augment.inverse_map gives them (None: identities).  src / dst [n, C, H, W] fp32 on the device, out of place; batches above 16
+    images run in chunks"""
+    code, images, field, steps = _field_args("warp_field", src, dst, kind, params, fired, pre_maps, 4)
+    assert src.dtype == torch.float32, src.dtype
+    n, Cc, H, W = src.shape
+    per = Cc * H * W
+    for at in range(0, n, L.FIELD_MAX_IMAGES):
+        m = min(L.FIELD_MAX_IMAGES, n - at)
+        check(lib.unet_warp_field(src.data_ptr() + at * per * 4, dst.data_ptr() + at * per * 4, m, Cc, H, W, code,
+                                  C.cast(C.byref(images, at * C.sizeof(L.FieldImage)), C.POINTER(L.FieldImage)),
+                                  None if field is None else field.data_ptr() + at * 2 * H * W * 4, steps[0], steps[1], int(interp),
+                                  int(border), float(fill), _stream()), "warp_field")
+
+
+def warp_field_mask(src: torch.Tensor, dst: torch.Tensor, kind: str, params, fired, pre_maps=None, border: int = 4, fill: float = 0.0):
+    """the nearest-neighbour field warp of masks [n, H, W] int64 or fp32, same arguments as warp_field"""
+    code, images, field, steps = _field_args("warp_field_mask", src, dst, kind, params, fired, pre_maps, 3)
+    assert src.dtype in (torch.int64, torch.float32), src.dtype
+    n, H, W = src.shape
+    es = src.element_size()
+    for at in range(0, n, L.FIELD_MAX_IMAGES):
+        m = min(L.FIELD_MAX_IMAGES, n - at)
+        check(lib.unet_warp_field_mask(src.data_ptr() + at * H * W * es, dst.data_ptr() + at * H * W * es, int(src.dtype == torch.float32),
+                                       m, H, W, code, C.cast(C.byref(images, at * C.sizeof(L.FieldImage)), C.POINTER(L.FieldImage)),
+                                       None if field is None else field.data_ptr() + at * 2 * H * W * 4, steps[0], steps[1], int(border),
+                                       float(fill), _stream()), "warp_field_mask")
+
+
+def elastic_field(field: torch.Tensor, workspace: torch.Tensor, keys, alpha, fired, same_dxdy: bool, taps):
+    """field [n, 2, H, W] fp32 on the device = the ElasticTransform displacements of n images (include/unet_hip.h): keys [n, 2] Philox
+    key words, alpha a scalar or [n], fired [n] (false: zeros), taps an odd number (at most 401) of fp32 filter taps; workspace: a device
+    tensor of the field's shape for the row-pass result.  Batches above 64 images run in chunks"""
+    import numpy as np
+    if not (field.is_cuda and workspace.is_cuda):
+        raise RuntimeError(f"elastic_field: the field is made on the device only (HIP, no CPU fallback); got {field.device} / "
+                           f"{workspace.device} tensors")
+    assert field.dim() == 4 and field.shape[1] == 2 and field.is_contiguous() and field.dtype == torch.float32, (field.shape, field.dtype)
+    assert workspace.shape == field.shape and workspace.is_contiguous() and workspace.dtype == torch.float32, (workspace.shape, workspace.dtype)
+    n, _, H, W = field.shape
+    taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+    if len(taps) > L.ELASTIC_MAX_KSIZE or len(taps) % 2 == 0:
+        raise ValueError(f"elastic_field: {len(taps)} taps (odd, at most {L.ELASTIC_MAX_KSIZE})")
+    keys = np.asarray(keys, dtype=np.int64).reshape(n, 2)
+    alphas = np.broadcast_to(np.asarray(alpha, dtype=np.float32), (n,))
+    flags = [bool(v) for v in fired]
+    assert len(flags) == n, (len(flags), n)
+    images = (L.ElasticImage * n)()
+    for j in range(n):
+        images[j] = L.ElasticImage(int(keys[j, 0]) & 0xffffffff, int(keys[j, 1]) & 0xffffffff, float(alphas[j]), int(flags[j]), int(bool(same_dxdy)))
+    per = 2 * H * W * 4
+    for at in range(0, n, L.ELASTIC_MAX_IMAGES):
+        m = min(L.ELASTIC_MAX_IMAGES, n - at)
+        check(lib.unet_elastic_field(field.data_ptr() + at * per, workspace.data_ptr() + at * per, m, H, W,
+                                     C.cast(C.byref(images, at * C.sizeof(L.ElasticImage)), C.POINTER(L.ElasticImage)),
+                                     taps.ctypes.data_as(L.c_float_p), len(taps), _stream()), "elastic_field")
+
+
 # ------------------------------------------------------------------ pixel-level augmentation (csrc/pixel_aug.hip)
 
 def _pixel_pieces(what: str, ops_: list, Cc: int) -> list:
