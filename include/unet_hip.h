@@ -640,6 +640,30 @@ int unet_relu_mask_bf16(const unet_bf16* g, int g_cs, int g_co, const unet_bf16*
 int unet_dot_bf16(const unet_bf16* x, int x_cs, int x_co, const unet_bf16* y, int y_cs, int y_co, long long P, int C, float* out, float* workspace, void* stream);
 int unet_cast_slice_bf16(const float* x, int x_cs, int x_co, unet_bf16* y, int y_cs, int y_co, long long P, int C, void* stream);
 
+/* ------------------------------------------------- class-mask post-processing --
+ * csrc/postprocess.hip (unet_amd/postprocess.py).  Masks are contiguous uint8 [H, W], H * W <= 2^31 - 1; labels / sizes are
+ * int32 [H, W] (labels 16-byte aligned), keys uint64 [H, W]; counters is int32[4] on the device: {components merged, small components
+ * not merged, give-up code, 0}.  frozen_class: -1 (none) or 0..255.  All workspace belongs to the caller.
+ * unet_cc_label: labels[p] = the smallest linear index y * W + x of p's component (equal class, 4- / 8-adjacency); resets counters.
+ *   Launches: tiles of unet_cc_tile_shape in LDS, border merge (atomicMin on the parent array = labels), flatten.
+ * unet_cc_sizes: sizes[l] = pixel count of the component with root label l, 0 at every other index.
+ * unet_sieve_round: one round on `in`: label + sizes + per small component (size < min_pixels, class != frozen_class) the edge-adjacent
+ *   component with the largest key (size << 32 | 0xFFFFFFFF - label), class != frozen_class, by a 64-bit atomicMax; a small component
+ *   whose best key exceeds its own takes that neighbour's class in `out` (!= in).  counters[0] / [1] = components that merged / stayed
+ *   small.  out == NULL: a counting pass (label, sizes, counters[1] = small components; keys may be NULL).  min_pixels >= 2.
+ * unet_majority_filter: out (!= in) = the class with the highest count in the k x k window (k odd, 3..15) clipped to the raster; ties: the
+ *   centre's class if tied, else the smallest id; frozen_class pixels neither vote nor change.
+ * unet_postprocess_counters: copies counters to host4 and waits for the stream; a give-up code (a find / union loop that ran H * W
+ *   steps) returns UNET_E_HIP with unet_last_error set.
+ * Bad arguments return -1 before any launch. */
+void unet_cc_tile_shape(int* th, int* tw);
+int unet_cc_label(const uint8_t* mask, int H, int W, int connectivity, int32_t* labels, int32_t* counters, void* stream);
+int unet_cc_sizes(const int32_t* labels, int H, int W, int32_t* sizes, void* stream);
+int unet_sieve_round(const uint8_t* in, uint8_t* out, int H, int W, int connectivity, long long min_pixels, int frozen_class,
+                     int32_t* labels, int32_t* sizes, unsigned long long* keys, int32_t* counters, void* stream);
+int unet_majority_filter(const uint8_t* in, uint8_t* out, int H, int W, int k, int frozen_class, void* stream);
+int unet_postprocess_counters(const int32_t* counters, int32_t* host4, void* stream);
+
 /* ------------------------------------------------------ GeoTIFF codecs --
  * Host-side (no device code) strip / tile decoders of unet_amd/tiffio.py.  Replaces what GDAL / rasterio do when the reference opens a
  * compressed raster (create_tiles_unet.py:252-434: gdal.Open / ReadAsArray; data.py:18-28: rasterio.open().read()).  Deflate is zlib.

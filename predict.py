@@ -29,6 +29,11 @@ window side / 8, ``unet_amd/mosaic.py``), as nnU-Net and MONAI's sliding-window 
 with half their context -- count less than the same pixels seen from the middle of the next window and the seams fade.  The weighted sum
 and the weight sum are accumulated on the device in the same order as the mean (``unet_mosaic_accumulate_windows_weighted``, the weighted
 slab add and finalisation), so N ranks equal 1 rank bit for bit here too.  Refused (ValueError) for ``large_file`` and per-tile outputs.
+
+And ``postprocess=`` (None | ``unet_amd.postprocess.PostProcess`` | a dict of its arguments): a majority filter and / or a small-region sieve
+of the merged class mask on the device (``unet_amd/postprocess.py``), on rank 0, on the assembled mask -- after the rows of the other ranks
+have arrived and before ``store_tif`` -- so N ranks equal 1 rank by construction.  With one rank the mask goes from the argmax to the filters
+without leaving the device.  Only for the class mask of a merged prediction (ValueError otherwise, before the model is loaded).
 """
 from __future__ import annotations
 
@@ -47,6 +52,7 @@ import torch
 from unet_amd import ops
 from unet_amd.feed import BatchFeeder, default_workers, torch_samples
 from unet_amd.learner import load_learner, open_tile
+from unet_amd.postprocess import check_postprocess
 from unet_amd.mosaic import MergePlan, blend_profile, check_blend, keep_windows, merge_order, sliding_windows
 from unet_amd.tiffio import read_tiff, tiff_info, write_tiff
 from unet_amd.tta import parse as tta_codes
@@ -201,8 +207,9 @@ class _Merge:
             else:
                 ops.mosaic_accumulate_weighted(slab, self._profile(h), self._profile(w), self.mosaic, self.count, self.wsum, y0 - self.lo, x0)
 
-    def finish(self, want):
-        """want: "argmax" | "all" | int class index.  Returns (on rank 0) the full-size numpy array, None elsewhere."""
+    def finish(self, want, postprocess=None, timing: Optional[dict] = None):
+        """want: "argmax" | "all" | int class index.  Returns (on rank 0) the full-size numpy array, None elsewhere.  postprocess: a
+        PostProcess applied to the assembled class mask on rank 0 (want == "argmax" only: check_postprocess)"""
         rows, MW, MH = self.hi - self.lo, self.plan.MW, self.plan.MH
         if self.int8:
             merged, counter = self.mosaic[:, :rows].cpu().numpy(), self.count[:, :rows].cpu().numpy()
@@ -217,7 +224,18 @@ class _Merge:
             elif rows > 0:
                 ops.mosaic_finalize_rows_weighted(self.mosaic, self.count, self.wsum, 0, rows, am, fill=-9999.0 if self.raw else None)
             part = am[:rows] if want == "argmax" else (self.mosaic[:, :rows] if want == "all" else self.mosaic[want, :rows])
-        return self._gather_rows(part, want == "all")
+        if postprocess is None:
+            return self._gather_rows(part, want == "all")
+        # one rank: the mask goes from the argmax to the filters on the device; N ranks: rank 0 uploads the assembled mask again
+        full = part if self.world == 1 else self._gather_rows(part, False)
+        if full is None:
+            return None
+        t0 = time.perf_counter()
+        out, info = postprocess.run(torch.as_tensor(full).to(self.dev))
+        out = out.cpu().numpy()
+        if timing is not None:
+            timing.update(postprocess_seconds=time.perf_counter() - t0, postprocess=info)
+        return out
 
     def _gather_rows(self, part: torch.Tensor, planes: bool):
         """row strips of the ranks -> one array on rank 0 (only the requested band(s) travel)"""
@@ -246,11 +264,11 @@ class _Merge:
 
 
 def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch, make_input: Callable, want, timing: Optional[dict] = None,
-               tta: Optional[Tuple[int, ...]] = None, blend: str = "mean"):
+               tta: Optional[Tuple[int, ...]] = None, blend: str = "mean", postprocess=None):
     """make_input(first, n, n_pad) -> ops.WindowBatch of placements [first, first + n) padded to n_pad windows (so that every
     forward runs on ONE batch geometry and no second set of activation buffers is allocated).  tta: parsed codes -- every batch runs
     len(tta) forwards of that same geometry and the averaged probabilities take the place of the softmax in the merge.  blend: "mean" |
-    "gaussian" (unet_amd/mosaic.py)"""
+    "gaussian" (unet_amd/mosaic.py).  postprocess: a checked PostProcess or None"""
     mg = _Merge(model, places, MH, MW, regression, int8_merge, rank, world, blend)
     t0 = time.perf_counter()
     batches = mg.plan.batches(rank, batch)
@@ -267,7 +285,7 @@ def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch
     mg.exchange()
     if timing is not None and not int8_merge and mg.hi > mg.lo:      # coverage of this rank's strip (before the division consumes nothing of it)
         timing.update(hits_min=int(mg.count.min().item()), hits_max=int(mg.count.max().item()))
-    out = mg.finish(want)
+    out = mg.finish(want, postprocess, timing)
     if timing is not None:
         torch.cuda.synchronize()
         timing.update(seconds=time.perf_counter() - t0, windows_this_rank=sum(n for _, n in batches), windows=len(mg.plan.places),
@@ -323,7 +341,7 @@ def _raster_plan(wins: np.ndarray, size: int, H: int, W: int, batch_size: int):
 def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_empty: float = 0.9, dtype: str = "int8", nodata=None,
                    regression: bool = False, all_classes: bool = False, specific_class: Optional[int] = None, large_file: bool = False,
                    batch_size: int = 16, out_path=None, class_zero: bool = False, timing: Optional[dict] = None,
-                   batch_invariant: bool = False, tta=None, blend: str = "mean"):
+                   batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -344,10 +362,14 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     blend    "mean" (the reference's merge: unweighted mean of the windows that cover a pixel) | "gaussian": every window's contribution
              is weighted with a centre-peaked Gaussian importance map (sigma = window side / 8, unet_amd/mosaic.py blend_profile) and the
              pixel is the weighted mean; not with large_file (ValueError)
+    postprocess  None | PostProcess | dict of its arguments (unet_amd/postprocess.py): majority filter and / or small-region sieve of the
+             merged class mask on the device, before it is returned / written; only for the class mask (not regression, all_classes,
+             specific_class: ValueError); timing gains postprocess_seconds and postprocess (the sieve's info)
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
     check_blend(blend, large_file)
+    post = check_postprocess(postprocess, regression, all_classes, specific_class)
     model = getattr(model, "model", model)
     codes = tta_codes(tta, [(size, size)])
     rank, _, world = _dist_ctx()
@@ -389,7 +411,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     want = _want(regression, all_classes, specific_class)
     with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
         out = _run_merge(model, places, MH, MW, regression, bool(large_file and not regression), rank, world, batch_size, make_input, want, timing,
-                         codes, blend)
+                         codes, blend, post)
     if rank == 0 and out_path is not None:
         ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
         store_tif(out_path, out, ogt, tags, -9999 if regression else None, class_zero)
@@ -548,12 +570,15 @@ def _tile_windows(batch_size: int, device, div255_twice: bool) -> Callable:
 
 def save_predictions(predict_model, predict_path, regression, merge=False, all_classes=False, specific_class=None, large_file=False,
                      AOI=None, year=None, validation_vision=True, class_zero=False, batch_size=16, timing: Optional[dict] = None,
-                     batch_invariant: bool = False, tta=None, blend: str = "mean"):
+                     batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None):
     """tta: None | "flips" | "d4" | a tuple of D4 codes (see predict_raster and unet_amd/tta.py), merged and per-tile outputs alike.
     blend: "mean" | "gaussian" (see predict_raster): how the windows of a merged prediction combine; only with merge=True (per-tile
     outputs have no overlap) and not with large_file (ValueError before the model is loaded).
+    postprocess: None | PostProcess | dict of its arguments (see predict_raster): only with merge=True and for the class mask (ValueError
+    before the model is loaded).
     validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
     check_blend(blend, large_file, merge)
+    post = check_postprocess(postprocess, regression, all_classes, specific_class, merge)
     rank, local_rank, world = _dist_ctx()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model
@@ -571,7 +596,7 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     windows = _tile_windows(batch_size, model._device, learn.dls.train_ds.dtype == "int16")
     if merge:
         out, gt = _save_merged(model, tiles, geos, windows, rank, world, regression, _want(regression, all_classes, specific_class),
-                               bool(large_file and not regression), batch_size, batch_invariant, codes, blend, timing)
+                               bool(large_file and not regression), batch_size, batch_invariant, codes, blend, timing, post)
     else:
         _save_tiles(model, tiles, geos, windows, rank, world, output_folder, regression, all_classes, specific_class, large_file, class_zero,
                     batch_size, batch_invariant, codes)
@@ -592,7 +617,7 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
 
 
 def _save_merged(model, tiles, geos, windows: Callable, rank, world, regression, want, int8_merge, batch_size, batch_invariant, codes, blend,
-                 timing):
+                 timing, postprocess=None):
     """overlap merge (predict.py:257-355) of this rank's share of the tiles -> (merged array on rank 0, None elsewhere; geotransform of
     the mosaic).  The extent follows from the tiles' geotransforms and sizes, which are known from the headers BEFORE any tile is
     predicted: every batch is accumulated into the device mosaic as soon as it is computed and its probabilities are dropped (the
@@ -625,7 +650,8 @@ def _save_merged(model, tiles, geos, windows: Callable, rank, world, regression,
             return windows(d, n)
 
         with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):          # (see predict_raster)
-            out = _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch_size, make_input, want, timing, codes, blend)
+            out = _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch_size, make_input, want, timing, codes, blend,
+                             postprocess)
     return out, [ulx_full, xres, 0.0, uly_full, 0.0, yres]
 
 

@@ -229,6 +229,12 @@ _sig = {
     "unet_mosaic_accumulate_weighted": (i, [vp, i, i, i, vp, vp, vp, vp, vp, i, i, i, i, vp]),
     "unet_mosaic_accumulate_windows_weighted": (i, [vp, i, i, i, i, i, vp, i, i, i, i, vp, vp, i, i, i, i, vp, vp, vp, vp]),
     "unet_mosaic_finalize_rows_weighted": (i, [vp, vp, vp, i, i, i, i, i, vp, c_float_p, vp]),
+    "unet_cc_tile_shape": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "unet_cc_label": (i, [vp, i, i, i, vp, vp, vp]),
+    "unet_cc_sizes": (i, [vp, i, i, vp, vp]),
+    "unet_sieve_round": (i, [vp, vp, i, i, i, ll, i, vp, vp, vp, vp, vp]),
+    "unet_majority_filter": (i, [vp, vp, i, i, i, i, vp]),
+    "unet_postprocess_counters": (i, [vp, C.POINTER(C.c_int32), vp]),
 }
 # bf16-storage twins: same argument lists (every tensor is a void pointer on this side)
 for _n in ("bn_stats", "affine_act", "bn_bwd_reduce", "bn_bwd_apply", "maxpool3x3s2", "maxpool3x3s2_bwd", "avgpool2_ceil",

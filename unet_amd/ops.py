@@ -1294,3 +1294,110 @@ def mosaic_finalize_rows_weighted(mosaic: torch.Tensor, count: torch.Tensor, wsu
     fp = None if fill is None else C.byref(C.c_float(float(fill)))
     check(lib.unet_mosaic_finalize_rows_weighted(mosaic.data_ptr(), count.data_ptr(), wsum.data_ptr(), Cc, MH, MW, row0, nrows, _p(amax),
                                                  None if fp is None else C.cast(fp, L.c_float_p), _stream()), "mosaic_finalize_rows_weighted")
+
+
+# ---------------------------------------------------------------------------------------------- class-mask post-processing (csrc/postprocess.hip)
+
+MASK_MAX_PIXELS = 2 ** 31 - 1
+
+
+def cc_tile_shape():
+    """(rows, columns) of the tile that the labelling kernel holds in LDS"""
+    th, tw = C.c_int(0), C.c_int(0)
+    lib.unet_cc_tile_shape(C.byref(th), C.byref(tw))
+    return th.value, tw.value
+
+
+def check_mask_shape(what: str, shape):
+    """[H, W] with 1 <= H * W <= 2^31 - 1 (labels are int32 linear indices): refused from the shape alone"""
+    if len(shape) != 2 or int(shape[0]) < 1 or int(shape[1]) < 1:
+        raise ValueError(f"{what}: expected a non-empty [H, W] mask, got shape {tuple(shape)}")
+    if int(shape[0]) * int(shape[1]) > MASK_MAX_PIXELS:
+        raise ValueError(f"{what}: {int(shape[0])} x {int(shape[1])} px exceeds 2^31 - 1 pixels (labels are int32 linear indices)")
+
+
+def _pp_tensor(what: str, name: str, t: torch.Tensor, dtype, shape=None, numel=None):
+    if shape is not None:
+        check_mask_shape(what, shape)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise ValueError(f"{what}: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: {name} must live on the GPU, got device {t.device}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if numel is not None and t.numel() < numel:
+        raise ValueError(f"{what}: {name} holds {t.numel()} elements, needs {numel}")
+
+
+def _pp_frozen(what: str, frozen) -> int:
+    if frozen is None:
+        return -1
+    if isinstance(frozen, bool) or not isinstance(frozen, int) or not 0 <= frozen <= 255:
+        raise ValueError(f"{what}: frozen_class must be None or an int in 0..255, got {frozen!r}")
+    return frozen
+
+
+def _pp_conn(what: str, connectivity) -> int:
+    if connectivity not in (4, 8):
+        raise ValueError(f"{what}: connectivity must be 4 or 8, got {connectivity!r}")
+    return int(connectivity)
+
+
+def cc_label(mask: torch.Tensor, connectivity: int, labels: torch.Tensor, counters: torch.Tensor):
+    """labels [H, W] int32 = smallest linear index of every pixel's component; counters int32[4] is reset (read it with postprocess_counters)"""
+    _pp_tensor("cc_label", "mask", mask, torch.uint8, mask.shape)
+    _pp_tensor("cc_label", "labels", labels, torch.int32, mask.shape)
+    _pp_tensor("cc_label", "counters", counters, torch.int32, numel=4)
+    H, W = mask.shape
+    check(lib.unet_cc_label(mask.data_ptr(), H, W, _pp_conn("cc_label", connectivity), labels.data_ptr(), counters.data_ptr(), _stream()), "cc_label")
+
+
+def cc_sizes(labels: torch.Tensor, sizes: torch.Tensor):
+    """sizes [H, W] int32: the pixel count of a component at its root label, 0 elsewhere"""
+    _pp_tensor("cc_sizes", "labels", labels, torch.int32, labels.shape)
+    _pp_tensor("cc_sizes", "sizes", sizes, torch.int32, labels.shape)
+    H, W = labels.shape
+    check(lib.unet_cc_sizes(labels.data_ptr(), H, W, sizes.data_ptr(), _stream()), "cc_sizes")
+
+
+def sieve_round(src: torch.Tensor, dst: Optional[torch.Tensor], connectivity: int, min_pixels: int, frozen_class, labels: torch.Tensor,
+                sizes: torch.Tensor, keys: Optional[torch.Tensor], counters: torch.Tensor):
+    """one sieve round src -> dst (unet_hip.h); dst None: a counting pass (counters[1] = small components of src)"""
+    _pp_tensor("sieve_round", "src", src, torch.uint8, src.shape)
+    if dst is not None:
+        _pp_tensor("sieve_round", "dst", dst, torch.uint8, src.shape)
+        _pp_tensor("sieve_round", "keys", keys, torch.int64, src.shape)
+        if dst.data_ptr() == src.data_ptr():
+            raise ValueError("sieve_round: src and dst must be different buffers")
+    _pp_tensor("sieve_round", "labels", labels, torch.int32, src.shape)
+    _pp_tensor("sieve_round", "sizes", sizes, torch.int32, src.shape)
+    _pp_tensor("sieve_round", "counters", counters, torch.int32, numel=4)
+    if isinstance(min_pixels, bool) or not isinstance(min_pixels, int) or min_pixels < 2:
+        raise ValueError(f"sieve_round: min_pixels must be an int >= 2, got {min_pixels!r}")
+    H, W = src.shape
+    check(lib.unet_sieve_round(src.data_ptr(), _p(dst), H, W, _pp_conn("sieve_round", connectivity), min(min_pixels, 2 ** 62),
+                               _pp_frozen("sieve_round", frozen_class), labels.data_ptr(), sizes.data_ptr(), _p(keys if dst is not None else None),
+                               counters.data_ptr(), _stream()), "sieve_round")
+
+
+def majority_filter(src: torch.Tensor, dst: torch.Tensor, k: int, frozen_class=None):
+    """dst = k x k majority vote of src (one Jacobi pass; unet_hip.h)"""
+    _pp_tensor("majority_filter", "src", src, torch.uint8, src.shape)
+    _pp_tensor("majority_filter", "dst", dst, torch.uint8, src.shape)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 3 or k > 15 or k % 2 == 0:
+        raise ValueError(f"majority_filter: k must be an odd int in 3..15, got {k!r}")
+    if dst.data_ptr() == src.data_ptr():
+        raise ValueError("majority_filter: src and dst must be different buffers")
+    H, W = src.shape
+    check(lib.unet_majority_filter(src.data_ptr(), dst.data_ptr(), H, W, k, _pp_frozen("majority_filter", frozen_class), _stream()), "majority_filter")
+
+
+def postprocess_counters(counters: torch.Tensor):
+    """(merged, small not merged) of the last round: the one host read (and stream sync) of a round.  A give-up code of the labelling
+    (a find / union loop that ran H * W steps) raises UnetHipError; it is never retried"""
+    _pp_tensor("postprocess_counters", "counters", counters, torch.int32, numel=4)
+    host = (C.c_int32 * 4)()
+    check(lib.unet_postprocess_counters(counters.data_ptr(), host, _stream()), "postprocess_counters")
+    return int(host[0]), int(host[1])
