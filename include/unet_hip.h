@@ -312,6 +312,15 @@ int unet_ce_fwd_parts(const float* z, int z_cs, int z_co, const int64_t* target,
 /* dz = gscale * w[y] * (softmax(z) - onehot(y)) / denom ; gscale multiplies (loss scaling / DDP averaging) */
 int unet_ce_bwd(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C,
                 const float* denom, float gscale, float* dz, int dz_cs, int dz_co, void* stream);
+/* The same three with ONE WEIGHT PER PIXEL, pixel_weight float [P] (never NULL), in place of the class weights: loss = sum pw * nll / sum pw,
+ * parts = the two sums, dz = gscale * pw * (softmax(z) - onehot(y)) / denom.  A target outside [0, C) is ignored whatever its weight is.
+ * Same kernels, reduction order and workspace (unet_ce_workspace): pw[p] == w[y(p)] reproduces the class-weighted results bit for bit. */
+int unet_ce_fwd_pw(const float* z, int z_cs, int z_co, const int64_t* target, const float* pixel_weight, long long P, int C,
+                   float* loss /*[1]*/, float* denom /*[1]*/, float* workspace, void* stream);
+int unet_ce_fwd_parts_pw(const float* z, int z_cs, int z_co, const int64_t* target, const float* pixel_weight, long long P, int C,
+                         float* numden /*[2]*/, float* workspace, void* stream);
+int unet_ce_bwd_pw(const float* z, int z_cs, int z_co, const int64_t* target, const float* pixel_weight, long long P, int C,
+                   const float* denom, float gscale, float* dz, int dz_cs, int dz_co, void* stream);
 /* FocalLossFlat(gamma, axis=1): the alternative classification loss the reference's configuration names (params_and_main.py:87-89).  fastai 2.5.1
  * losses.FocalLoss: ce = w[y] * nll per pixel (F.cross_entropy(weight, reduction="none"); train.py:211 assigns the class weights to every
  * loss), loss = mean over ALL P pixels of (1 - exp(-ce))^gamma * ce.  dz = gscale * d loss / d z.  workspace = unet_ce_workspace(P) floats.
@@ -611,6 +620,7 @@ int unet_nchw_to_nhwc_bf16(const float* x, unet_bf16* y, int y_cs, int y_co, int
 int unet_copy_slice_bf16(const unet_bf16* x, int x_cs, int x_co, unet_bf16* y, int y_cs, int y_co, long long P, int C, int accumulate, void* stream);
 int unet_ce_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C, const float* denom, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
 int unet_focal_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C, float gamma, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
+int unet_ce_bwd_pw_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* pixel_weight, long long P, int C, const float* denom, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
 int unet_dice_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, int B, long long HW, int C, int square_in_union, const float* coef, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
 int unet_combined_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, int B, long long HW, int C, float gamma, int square_in_union, const float* coef, float fscale, float dscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream);
 /* bf16 SelfAttention (round 3): the attention logits and the gradient of the attention weights stay fp32 (the products that make them write
@@ -663,6 +673,21 @@ int unet_sieve_round(const uint8_t* in, uint8_t* out, int H, int W, int connecti
                      int32_t* labels, int32_t* sizes, unsigned long long* keys, int32_t* counters, void* stream);
 int unet_majority_filter(const uint8_t* in, uint8_t* out, int H, int W, int k, int frozen_class, void* stream);
 int unet_postprocess_counters(const int32_t* counters, int32_t* host4, void* stream);
+
+/* ------------------------------------------------------- border distance --
+ * csrc/edt.hip (unet_amd/border.py).  Masks are contiguous [B, H, W], uint8 or int64 (mask_is_int64), 1 <= H, W <= 8192.
+ * A pixel is a BORDER pixel when one of its 4-neighbours inside the image has another value; with exclude >= 0 a pair in which either
+ * value equals exclude does not count (-1: none).
+ * unet_border_edt: d2 int32 [B, H, W] = the squared Euclidean distance to the nearest border pixel of the same image (0 on a border
+ *   pixel), INT32_MAX in an image without one.  Exact and independent of the schedule (integers, no atomics).  Two launches: a column
+ *   pass into the uint16 workspace (unet_edt_workspace BYTES, 2-byte aligned, the caller's), a row pass with the row in LDS.
+ * unet_border_weight: pw[p] = class_w[y] + w0 * exp(-d2[p] / (2 sigma^2)), the weight map of the U-Net paper; class_w [C] or NULL (ones);
+ *   a target outside [0, C) gives 0; d2 == INT32_MAX gives a border term of exactly 0.  One launch.
+ * Bad arguments return -1 before any launch. */
+size_t unet_edt_workspace(int B, int H, int W);   /* bytes; 0 for a shape outside the limits */
+int unet_border_edt(const void* mask, int mask_is_int64, int B, int H, int W, int exclude, int32_t* d2, void* workspace, void* stream);
+int unet_border_weight(const int32_t* d2, const int64_t* target, const float* class_w, int C, float w0, double sigma, long long P,
+                       float* pw, void* stream);
 
 /* ------------------------------------------------------ GeoTIFF codecs --
  * Host-side (no device code) strip / tile decoders of unet_amd/tiffio.py.  Replaces what GDAL / rasterio do when the reference opens a

@@ -54,6 +54,8 @@ LR_FINDER = None               # None, "minimum", "steep", "valley", "slide"
 VALID_SCENES = ["vali"]
 loss_func = None               # None = CrossEntropyLossFlat(axis=1) (the reference's default object) | FocalLossFlat(gamma=2, axis=1) | DiceLoss(axis=1) | CombinedLoss(axis=1) (from unet_amd.learner);
                                # regression: MSELossFlat(axis=1), L1LossFlat
+                               # BorderWeightedCrossEntropy(axis=1, w0=10, sigma=5, exclude=None): the U-Net paper's cross-entropy with a per-pixel
+                               # weight that is large near class borders (thin gaps between crowns, roofs, parcels); exclude=0 with class_zero
 monitor = "valid_loss"         # 'dice_multi', 'r2_score', 'train_loss', 'valid_loss'
 all_classes = False
 specific_class = None

@@ -188,6 +188,9 @@ _sig = {
     "unet_ce_fwd": (i, [vp, i, i, vp, vp, ll, i, vp, vp, vp, vp]),
     "unet_ce_fwd_parts": (i, [vp, i, i, vp, vp, ll, i, vp, vp, vp]),
     "unet_ce_bwd": (i, [vp, i, i, vp, vp, ll, i, vp, f, vp, i, i, vp]),
+    "unet_ce_fwd_pw": (i, [vp, i, i, vp, vp, ll, i, vp, vp, vp, vp]),
+    "unet_ce_fwd_parts_pw": (i, [vp, i, i, vp, vp, ll, i, vp, vp, vp]),
+    "unet_ce_bwd_pw": (i, [vp, i, i, vp, vp, ll, i, vp, f, vp, i, i, vp]),
     "unet_focal_fwd": (i, [vp, i, i, vp, vp, ll, i, f, vp, vp, vp]),
     "unet_focal_bwd": (i, [vp, i, i, vp, vp, ll, i, f, f, vp, i, i, vp]),
     "unet_dice_workspace": (sz, [i, ll, i]),
@@ -235,10 +238,13 @@ _sig = {
     "unet_sieve_round": (i, [vp, vp, i, i, i, ll, i, vp, vp, vp, vp, vp]),
     "unet_majority_filter": (i, [vp, vp, i, i, i, i, vp]),
     "unet_postprocess_counters": (i, [vp, C.POINTER(C.c_int32), vp]),
+    "unet_edt_workspace": (sz, [i, i, i]),
+    "unet_border_edt": (i, [vp, i, i, i, i, i, vp, vp, vp]),
+    "unet_border_weight": (i, [vp, vp, vp, i, f, C.c_double, ll, vp, vp]),
 }
 # bf16-storage twins: same argument lists (every tensor is a void pointer on this side)
 for _n in ("bn_stats", "affine_act", "bn_bwd_reduce", "bn_bwd_apply", "maxpool3x3s2", "maxpool3x3s2_bwd", "avgpool2_ceil",
-           "avgpool2_ceil_bwd", "shuffle_blur", "shuffle_blur_bwd", "shuffle_bwd_xmask", "resize_nearest", "resize_nearest_bwd", "nchw_to_nhwc", "copy_slice", "ce_bwd", "focal_bwd",
+           "avgpool2_ceil_bwd", "shuffle_blur", "shuffle_blur_bwd", "shuffle_bwd_xmask", "resize_nearest", "resize_nearest_bwd", "nchw_to_nhwc", "copy_slice", "ce_bwd", "ce_bwd_pw", "focal_bwd",
            "dice_bwd", "combined_bwd"):
     _sig[f"unet_{_n}_bf16"] = _sig[f"unet_{_n}"]
 for _n in ("pack_weights_strided", "row_softmax", "row_softmax_bwd", "relu_mask", "dot"):

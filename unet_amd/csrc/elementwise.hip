@@ -980,6 +980,9 @@ __global__ __launch_bounds__(256) void relu_mask_kernel(const T* __restrict__ g,
 // ---------------------------------------------------------------- loss
 constexpr int CE_MAXC = 64;
 
+// PW: `weight` holds one weight per pixel ([P], never null) instead of one per class ([C] or null).  Everything else -- the order of the
+// sums, the grid, the workspace -- is shared, so a map with pw[p] == w[y(p)] reproduces the class-weighted kernels bit for bit.
+template <bool PW>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ z, int z_cs, int z_co, const int64_t* __restrict__ target,
                                                      const float* __restrict__ weight, long long P, int C, float* __restrict__ part) {
     float num = 0.f, den = 0.f;
@@ -992,7 +995,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ z
         float s = 0.f;
         for (int c = 0; c < C; ++c) s += expf(zp[c] - m);
         const float nll = (m + logf(s)) - zp[y];
-        const float w = weight ? weight[y] : 1.f;
+        const float w = PW ? weight[p] : (weight ? weight[y] : 1.f);
         num += w * nll;
         den += w;
     }
@@ -1027,7 +1030,7 @@ __global__ __launch_bounds__(64) void ce_finalize_kernel(const float* __restrict
     if (numden) { numden[0] = (float)n; numden[1] = (float)d; }
 }
 
-template <typename T>
+template <typename T, bool PW>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ z, int z_cs, int z_co, const int64_t* __restrict__ target,
                                                      const float* __restrict__ weight, long long P, int C, const float* __restrict__ denom,
                                                      float gscale, T* __restrict__ dz, int dz_cs, int dz_co) {
@@ -1044,7 +1047,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ z
         for (int c = 1; c < C; ++c) m = fmaxf(m, zp[c]);
         float s = 0.f;
         for (int c = 0; c < C; ++c) s += expf(zp[c] - m);
-        const float w = (weight ? weight[y] : 1.f) * inv;
+        const float w = (PW ? weight[p] : (weight ? weight[y] : 1.f)) * inv;
         const float is = 1.f / s;
         for (int c = 0; c < C; ++c) st1(dp + c, w * (expf(zp[c] - m) * is - (c == y ? 1.f : 0.f)));
     }
@@ -1992,44 +1995,62 @@ static int ce_rows(long long P) {
 
 extern "C" size_t unet_ce_workspace(long long P) { return (size_t)2 * ce_rows(P); }
 
-extern "C" int unet_ce_fwd(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C, float* loss,
-                           float* denom, float* workspace, void* stream) {
-    UNET_CHECK_ARG(z && target && loss && denom && workspace && P > 0 && C > 0 && C <= CE_MAXC, "ce_fwd: bad args");
-    UNET_CHECK_ARG(z_co >= 0 && z_co + C <= z_cs, "ce_fwd: bad slice");
+template <bool PW>
+static int ce_fwd_impl(const char* what, const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C,
+                       float* loss, float* denom, float* numden, float* workspace, void* stream) {
+    UNET_CHECK_ARG(z && target && (numden || (loss && denom)) && workspace && (weight || !PW) && P > 0 && C > 0 && C <= CE_MAXC, "%s: bad args", what);
+    UNET_CHECK_ARG(z_co >= 0 && z_co + C <= z_cs, "%s: bad slice", what);
     const int rows = ce_rows(P);
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3(rows), dim3(256), 0, ST, z, z_cs, z_co, target, weight, P, C, workspace);
+    hipLaunchKernelGGL(ce_fwd_kernel<PW>, dim3(rows), dim3(256), 0, ST, z, z_cs, z_co, target, weight, P, C, workspace);
     UNET_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(64), 0, ST, workspace, rows, loss, denom, (float*)nullptr);
+    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(64), 0, ST, workspace, rows, loss, denom, numden);
     UNET_CHECK_LAUNCH();
     return UNET_OK;
+}
+
+extern "C" int unet_ce_fwd(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C, float* loss,
+                           float* denom, float* workspace, void* stream) {
+    UNET_CHECK_ARG(loss && denom, "ce_fwd: bad args");
+    return ce_fwd_impl<false>("ce_fwd", z, z_cs, z_co, target, weight, P, C, loss, denom, nullptr, workspace, stream);
 }
 
 extern "C" int unet_ce_fwd_parts(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C,
                                  float* numden, float* workspace, void* stream) {
-    UNET_CHECK_ARG(z && target && numden && workspace && P > 0 && C > 0 && C <= CE_MAXC, "ce_fwd_parts: bad args");
-    UNET_CHECK_ARG(z_co >= 0 && z_co + C <= z_cs, "ce_fwd_parts: bad slice");
-    const int rows = ce_rows(P);
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3(rows), dim3(256), 0, ST, z, z_cs, z_co, target, weight, P, C, workspace);
-    UNET_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(64), 0, ST, workspace, rows, (float*)nullptr, (float*)nullptr, numden);
-    UNET_CHECK_LAUNCH();
-    return UNET_OK;
+    UNET_CHECK_ARG(numden, "ce_fwd_parts: bad args");
+    return ce_fwd_impl<false>("ce_fwd_parts", z, z_cs, z_co, target, weight, P, C, nullptr, nullptr, numden, workspace, stream);
 }
 
-template <typename T>
+// the same with one weight per pixel: loss = sum pw * nll / sum pw (a target outside [0, C) is ignored whatever its weight says)
+extern "C" int unet_ce_fwd_pw(const float* z, int z_cs, int z_co, const int64_t* target, const float* pixel_weight, long long P, int C,
+                              float* loss, float* denom, float* workspace, void* stream) {
+    UNET_CHECK_ARG(loss && denom, "ce_fwd_pw: bad args");
+    return ce_fwd_impl<true>("ce_fwd_pw", z, z_cs, z_co, target, pixel_weight, P, C, loss, denom, nullptr, workspace, stream);
+}
+
+extern "C" int unet_ce_fwd_parts_pw(const float* z, int z_cs, int z_co, const int64_t* target, const float* pixel_weight, long long P, int C,
+                                    float* numden, float* workspace, void* stream) {
+    UNET_CHECK_ARG(numden, "ce_fwd_parts_pw: bad args");
+    return ce_fwd_impl<true>("ce_fwd_parts_pw", z, z_cs, z_co, target, pixel_weight, P, C, nullptr, nullptr, numden, workspace, stream);
+}
+
+template <typename T, bool PW>
 static int ce_bwd_impl(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C,
                            const float* denom, float gscale, T* dz, int dz_cs, int dz_co, void* stream) {
-    UNET_CHECK_ARG(z && target && denom && dz && P > 0 && C > 0 && C <= CE_MAXC, "ce_bwd: bad args");
+    UNET_CHECK_ARG(z && target && denom && dz && (weight || !PW) && P > 0 && C > 0 && C <= CE_MAXC, "ce_bwd: bad args");
     UNET_CHECK_ARG(z_co >= 0 && z_co + C <= z_cs && dz_co >= 0 && dz_co + C <= dz_cs, "ce_bwd: bad slice");
-    hipLaunchKernelGGL((ce_bwd_kernel<T>), dim3(ew_grid(P, 256)), dim3(256), 0, ST, z, z_cs, z_co, target, weight, P, C, denom, gscale, dz, dz_cs,
+    hipLaunchKernelGGL((ce_bwd_kernel<T, PW>), dim3(ew_grid(P, 256)), dim3(256), 0, ST, z, z_cs, z_co, target, weight, P, C, denom, gscale, dz, dz_cs,
                        dz_co);
     UNET_CHECK_LAUNCH();
     return UNET_OK;
 }
 extern "C" int unet_ce_bwd(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C,
-                           const float* denom, float gscale, float* dz, int dz_cs, int dz_co, void* stream) { return ce_bwd_impl<float>(z, z_cs, z_co, target, weight, P, C, denom, gscale, dz, dz_cs, dz_co, stream); }
+                           const float* denom, float gscale, float* dz, int dz_cs, int dz_co, void* stream) { return ce_bwd_impl<float, false>(z, z_cs, z_co, target, weight, P, C, denom, gscale, dz, dz_cs, dz_co, stream); }
 extern "C" int unet_ce_bwd_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C,
-                           const float* denom, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream) { return ce_bwd_impl<unet_bf16>(z, z_cs, z_co, target, weight, P, C, denom, gscale, dz, dz_cs, dz_co, stream); }
+                           const float* denom, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream) { return ce_bwd_impl<unet_bf16, false>(z, z_cs, z_co, target, weight, P, C, denom, gscale, dz, dz_cs, dz_co, stream); }
+extern "C" int unet_ce_bwd_pw(const float* z, int z_cs, int z_co, const int64_t* target, const float* pixel_weight, long long P, int C,
+                           const float* denom, float gscale, float* dz, int dz_cs, int dz_co, void* stream) { return ce_bwd_impl<float, true>(z, z_cs, z_co, target, pixel_weight, P, C, denom, gscale, dz, dz_cs, dz_co, stream); }
+extern "C" int unet_ce_bwd_pw_bf16(const float* z, int z_cs, int z_co, const int64_t* target, const float* pixel_weight, long long P, int C,
+                           const float* denom, float gscale, unet_bf16* dz, int dz_cs, int dz_co, void* stream) { return ce_bwd_impl<unet_bf16, true>(z, z_cs, z_co, target, pixel_weight, P, C, denom, gscale, dz, dz_cs, dz_co, stream); }
 
 extern "C" int unet_focal_fwd(const float* z, int z_cs, int z_co, const int64_t* target, const float* weight, long long P, int C, float gamma,
                               float* loss, float* workspace, void* stream) {

@@ -9,7 +9,8 @@ train_bn, moms`` (``train.py:148-154``); ``unfreeze`` (``:246``); ``fit_one_cycl
 ``get_preds``; ``summary``; callbacks ``SaveModelCallback(monitor, comp, fname)`` and ``CSVLogger`` (``train.py:209``);
 ``CrossEntropyLossFlat(axis=1, weight)`` with assignable ``.func.weight`` (``train.py:195,211``), ``FocalLossFlat(gamma, axis=1)``
 (``params_and_main.py:87-89``), ``DiceLoss(axis=1, smooth, reduction, square_in_union)``, ``CombinedLoss(axis=1, smooth, alpha)`` (focal +
-alpha * Dice, from fastai's documentation of DiceLoss); ``DiceMulti``.
+alpha * Dice, from fastai's documentation of DiceLoss), ``BorderWeightedCrossEntropy(axis=1, weight, w0, sigma, exclude)`` (the U-Net
+paper's border-weighted cross-entropy); ``DiceMulti``.
 """
 from __future__ import annotations
 
@@ -97,6 +98,32 @@ class FocalLossFlat(CrossEntropyLossFlat):
         """Generic path (torch autograd)."""
         ce = torch.nn.functional.cross_entropy(logits, targ.long(), weight=self._w(logits.device), reduction="none")
         return ((1 - torch.exp(-ce)) ** self.gamma * ce).mean()
+
+
+class BorderWeightedCrossEntropy(CrossEntropyLossFlat):
+    """The loss of the U-Net paper (Ronneberger et al. 2015, eq. 1-2): cross-entropy with one weight per pixel that is large near the class
+    borders, ``w(p) = weight[y(p)] + w0 * exp(-d(p)^2 / (2 sigma^2))``, loss = ``sum w nll / sum w``.  ``d`` is the Euclidean distance to the
+    nearest border pixel of the tile (unet_amd/border.py has the rules; ``exclude=0`` keeps edges against the NO_Data class out).  The map is
+    taken from the mask the step sees, after augmentation, on the device.  ``w0=10, sigma=5`` are the paper's.  ``.func.weight`` (train.py:211
+    assigns it for every loss) is the class term.  The paper's two-instance form ``(d1 + d2)^2``, the distances to the two nearest OBJECTS, is
+    out of scope: this loss knows classes, not instances.  Fused on the device (unet_border_edt, unet_border_weight, unet_ce_fwd_pw /
+    unet_ce_bwd_pw)."""
+
+    def __init__(self, axis: int = 1, weight: Optional[torch.Tensor] = None, w0: float = 10.0, sigma: float = 5.0, exclude: Optional[int] = None):
+        super().__init__(axis=axis, weight=weight)
+        from .border import check_border_params
+        self.w0, self.sigma, self.exclude = check_border_params(w0, sigma, exclude)
+
+    def __call__(self, logits: torch.Tensor, targ: torch.Tensor) -> torch.Tensor:
+        """Generic path (torch autograd): the same formula, the map from border_weight_map."""
+        from .border import border_weight_map
+        C = logits.shape[self.axis]
+        targ = targ.long()
+        w = self._w(targ.device)
+        pw = border_weight_map(targ, w, self.w0, self.sigma, self.exclude, n_classes=C).to(logits.device, logits.dtype)
+        valid = (targ >= 0) & (targ < C)
+        nll = torch.nn.functional.cross_entropy(logits, torch.where(valid, targ, -100), reduction="none")
+        return (pw * nll).sum() / pw.sum()
 
 
 class DiceLoss:
@@ -756,6 +783,10 @@ class Learner:
         return self.loss_func if isinstance(self.loss_func, CombinedLoss) else None
 
     @property
+    def _border(self) -> Optional[BorderWeightedCrossEntropy]:
+        return self.loss_func if isinstance(self.loss_func, BorderWeightedCrossEntropy) else None
+
+    @property
     def regression(self) -> bool:
         return isinstance(self.loss_func, _RegLoss)
 
@@ -801,6 +832,7 @@ class Learner:
             step.focal_gamma = self._focal_gamma
             step.dice = self._dice
             step.combined = self._combined
+            step.border = self._border
         n_iter = len(self.dls.train)
         total = max(1, n_epoch * n_iter)
         for cb in self.cbs:
@@ -885,6 +917,11 @@ class Learner:
                 ops.focal_fwd(z, yb, w, self._focal_gamma, loss, ctx.workspace(ops.ce_workspace(z.P)))
                 acc[0] += loss[0].double() * z.P
                 acc[1] += z.P
+            elif self._border is not None:               # the weighted mean with the tile's own weight map
+                pw = model.border_weights(yb, w, self._border, z.C)
+                ops.ce_fwd_pw(z, yb, pw, loss, denom, ctx.workspace(ops.ce_workspace(z.P)))
+                acc[0] += loss[0].double() * denom[0].double()
+                acc[1] += denom[0].double()
             else:
                 ops.ce_fwd(z, yb, w, loss, denom, ctx.workspace(ops.ce_workspace(z.P)))
                 acc[0] += loss[0].double() * denom[0].double()
@@ -1095,6 +1132,8 @@ class Learner:
                                  "square_in_union": cl.square_in_union,
                                  "class_weights": None if cl.func.weight is None else [float(v) for v in torch.as_tensor(cl.func.weight).cpu()]}}
                    if cl is not None else {}),
+                **({"border": {"w0": self._border.w0, "sigma": self._border.sigma, "exclude": self._border.exclude}}
+                   if self._border is not None else {}),
                 "self_attention": bool(getattr(m, "self_attention", False)), "act_dtype": getattr(m, "act_dtype", "f32")}
         p = Path(fname)
         p = p if p.is_absolute() else self.path / p
@@ -1138,7 +1177,7 @@ def load_learner(fname, device="cuda", act_dtype: Optional[str] = None) -> Learn
 
 
 def _loss_from_meta(meta: dict):
-    """the loss object an exported file describes (Learner.export); files without a "dice" or a "combined" key load as they always have"""
+    """the loss object an exported file describes (Learner.export); files without a "dice", "combined" or "border" key load as they always have"""
     if meta.get("regression"):
         return {"mse": MSELossFlat, "l1": L1LossFlat, "smoothl1": Smoothl1}[meta["regression"]](axis=1)
     if meta.get("dice") is not None:
@@ -1150,4 +1189,7 @@ def _loss_from_meta(meta: dict):
                             square_in_union=d["square_in_union"], weight=None if d["class_weights"] is None else torch.tensor(d["class_weights"]))
     w = meta.get("class_weights")
     wt = None if w is None else torch.tensor(w)
+    if meta.get("border") is not None:
+        d = meta["border"]
+        return BorderWeightedCrossEntropy(axis=1, weight=wt, w0=d["w0"], sigma=d["sigma"], exclude=d["exclude"])
     return CrossEntropyLossFlat(axis=1, weight=wt) if meta.get("focal_gamma") is None else FocalLossFlat(gamma=meta["focal_gamma"], axis=1, weight=wt)

@@ -463,9 +463,20 @@ class HipDynamicUnet(nn.Module):
             if p.grad is None or p.grad.data_ptr() != self.flat_grad.data_ptr() + 4 * o:
                 p.grad = self.flat_grad[o:o + n].view(p.shape)
 
+    def border_weights(self, y: torch.Tensor, weight: Optional[torch.Tensor], border, n_classes: int) -> torch.Tensor:
+        """float32 [P]: the border weight map of the int64 masks y [B, H, W] (unet_amd/border.py) in a persistent buffer of the context;
+        two C-ABI calls (three launches) on the current stream.  The distance transform's intermediate is the shared workspace."""
+        ctx = self.ctx
+        B, H, W = (int(v) for v in y.shape)
+        d2 = ctx.vec(self, "border_d2", y.numel(), dtype=torch.int32)
+        pw = ctx.vec(self, "border_pw", y.numel())
+        ops.border_edt(y, d2, ctx.workspace((ops.edt_workspace(B, H, W) + 3) // 4), border.exclude)
+        ops.border_weight(d2, y, weight, n_classes, border.w0, border.sigma, pw)
+        return pw
+
     def forward_loss_backward(self, x: torch.Tensor, y: torch.Tensor, weight: Optional[torch.Tensor] = None,
                               grad_scale: float = 1.0, reg_kind: Optional[str] = None, reg_beta: float = 0.5,
-                              world: int = 1, focal_gamma: Optional[float] = None, dice=None, combined=None) -> torch.Tensor:
+                              world: int = 1, focal_gamma: Optional[float] = None, dice=None, combined=None, border=None) -> torch.Tensor:
         """One fused training pass: logits -> loss -> backward into the flat gradient buffer.  Returns the loss as a 1-element
         device tensor (no host sync).  grad_scale multiplies the gradient.
         world > 1 (tile-DDP): the weighted cross-entropy is sum_r num_r / sum_r den_r over the ranks (den_r = sum of w[y] on
@@ -483,7 +494,19 @@ class HipDynamicUnet(nn.Module):
         alpha * dice in one loss kernel pair.  Each term keeps its own N-rank rule: ONE all-reduce of (focal, dice sum, count of the Dice
         terms), the focal term averaged over the ranks and its gradient pre-scaled by 1 / world, the Dice term summed ('mean': divided by
         the global count, as are its coefficients); alpha is applied on the device.
+        border: BorderWeightedCrossEntropy instead -- any object with .w0, .sigma and .exclude: the cross-entropy with one weight per pixel,
+        weight[y] + w0 * exp(-D^2 / (2 sigma^2)), D the distance to the nearest class border of the tile (unet_amd/border.py).  Border distance,
+        weight map, loss forward and backward are four C-ABI calls on the step's stream, no host sync.  A pixel's weight depends on its own
+        tile only, so the N-rank rule is the plain cross-entropy's: numerator and denominator all-reduced.
         Regression (reg_kind = "mse" | "l1" | "smoothl1", n_out = 1, float targets [B,H,W]): train.py:189-193."""
+        if border is not None:
+            if dice is not None or combined is not None or focal_gamma is not None or reg_kind is not None:
+                raise ValueError("the border-weighted cross-entropy is a loss of its own: it cannot be combined with dice=, combined=, "
+                                 "focal_gamma= or a regression loss")
+            if self.n_out > ops.CE_MAXC:
+                raise ValueError(f"the border-weighted cross-entropy supports at most {ops.CE_MAXC} classes, the model has {self.n_out}")
+            if not (border.w0 >= 0 and border.sigma > 0):
+                raise ValueError(f"the border-weighted cross-entropy needs w0 >= 0 and sigma > 0, not {border.w0!r} and {border.sigma!r}")
         if combined is not None:
             if dice is not None or focal_gamma is not None or reg_kind is not None:
                 raise ValueError("CombinedLoss is a loss of its own: it cannot be combined with dice=, focal_gamma= or a regression loss")
@@ -558,6 +581,20 @@ class HipDynamicUnet(nn.Module):
                 loss.div_(world)
                 grad_scale = grad_scale / world
             ops.focal_bwd(z, y, weight, focal_gamma, grad_scale, dz)
+        elif border is not None:
+            y = y.to(self._device, torch.int64).contiguous()
+            loss, denom = ctx.vec(self, "loss", 1), ctx.vec(self, "denom", 1)
+            pw = self.border_weights(y, weight, border, z.C)
+            if world > 1:
+                import torch.distributed as dist
+                nd = ctx.vec(self, "numden", 2)
+                ops.ce_fwd_parts_pw(z, y, pw, nd, ctx.workspace(ops.ce_workspace(P)))       # this rank's numerator and denominator
+                dist.all_reduce(nd)
+                denom.copy_(nd[1:2])
+                torch.div(nd[0:1], nd[1:2], out=loss)
+            else:
+                ops.ce_fwd_pw(z, y, pw, loss, denom, ctx.workspace(ops.ce_workspace(P)))
+            ops.ce_bwd_pw(z, y, pw, denom, grad_scale, dz)
         elif reg_kind is None:
             y = y.to(self._device, torch.int64).contiguous()
             loss, denom = ctx.vec(self, "loss", 1), ctx.vec(self, "denom", 1)

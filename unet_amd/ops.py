@@ -702,6 +702,49 @@ def ce_bwd(z: TS, target, weight, denom, gscale: float, dz: TS):
                           dz.co, _stream()), "ce_bwd")
 
 
+def _pw_args(what: str, z: TS, target: torch.Tensor, pixel_weight: torch.Tensor):
+    """one weight per pixel: float32 [P], contiguous, on the logits' device (the kernels index it by the pixel, not by the class)"""
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != z.P:
+        raise ValueError(f"{what}: target must be a contiguous int64 tensor of {z.P} pixels")
+    if not isinstance(pixel_weight, torch.Tensor) or pixel_weight.dtype != torch.float32:
+        raise ValueError(f"{what}: pixel_weight must be a float32 tensor, got {getattr(pixel_weight, 'dtype', type(pixel_weight))}")
+    if not pixel_weight.is_contiguous() or pixel_weight.numel() != z.P:
+        raise ValueError(f"{what}: pixel_weight must be contiguous with one weight per pixel ({z.P}), got {pixel_weight.numel()}")
+    if pixel_weight.device != z.buf.device or target.device != z.buf.device:
+        raise ValueError(f"{what}: target and pixel_weight must live on the logits' device {z.buf.device}")
+    if z.C > CE_MAXC:
+        raise ValueError(f"{what}: at most {CE_MAXC} classes, got {z.C}")
+
+
+def ce_fwd_pw(z: TS, target: torch.Tensor, pixel_weight: torch.Tensor, loss, denom, ws):
+    """loss[0] = sum pw * nll / sum pw, denom[0] = sum pw over the pixels whose target is in [0, C)"""
+    _need_f32("ce_fwd_pw", z)
+    _pw_args("ce_fwd_pw", z, target, pixel_weight)
+    if ws.numel() < ce_workspace(z.P):
+        raise ValueError(f"ce_fwd_pw: the workspace holds {ws.numel()} floats, needs {ce_workspace(z.P)}")
+    check(lib.unet_ce_fwd_pw(z.ptr, z.cs, z.co, target.data_ptr(), pixel_weight.data_ptr(), z.P, z.C, loss.data_ptr(), denom.data_ptr(),
+                             ws.data_ptr(), _stream()), "ce_fwd_pw")
+
+
+def ce_fwd_parts_pw(z: TS, target: torch.Tensor, pixel_weight: torch.Tensor, numden: torch.Tensor, ws):
+    """numden[0] = sum pw * nll, numden[1] = sum pw over this rank's pixels (tile-DDP: all-reduced before the division)"""
+    _need_f32("ce_fwd_parts_pw", z)
+    _pw_args("ce_fwd_parts_pw", z, target, pixel_weight)
+    if numden.numel() < 2 or ws.numel() < ce_workspace(z.P):
+        raise ValueError(f"ce_fwd_parts_pw: numden needs 2 floats and the workspace {ce_workspace(z.P)}, got {numden.numel()} and {ws.numel()}")
+    check(lib.unet_ce_fwd_parts_pw(z.ptr, z.cs, z.co, target.data_ptr(), pixel_weight.data_ptr(), z.P, z.C, numden.data_ptr(), ws.data_ptr(),
+                                   _stream()), "ce_fwd_parts_pw")
+
+
+def ce_bwd_pw(z: TS, target, pixel_weight: torch.Tensor, denom, gscale: float, dz: TS):
+    """dz = gscale * pw * (softmax(z) - onehot(y)) / denom[0]; dz fp32 or bf16"""
+    _pw_args("ce_bwd_pw", z, target, pixel_weight)
+    if dz.P != z.P or dz.C != z.C:
+        raise ValueError(f"ce_bwd_pw: dz is {dz.P} x {dz.C}, the logits are {z.P} x {z.C}")
+    check(_fn("ce_bwd_pw", dz)(z.ptr, z.cs, z.co, target.data_ptr(), pixel_weight.data_ptr(), z.P, z.C, denom.data_ptr(), gscale, dz.ptr, dz.cs,
+                               dz.co, _stream()), "ce_bwd_pw")
+
+
 def focal_fwd(z: TS, target: torch.Tensor, weight, gamma: float, loss, ws):
     """loss[0] = mean over all pixels of (1 - exp(-ce))^gamma * ce, ce = w[y] * nll (fastai FocalLossFlat(gamma, axis=1))"""
     _need_f32("focal_fwd", z)
@@ -1401,3 +1444,75 @@ def postprocess_counters(counters: torch.Tensor):
     host = (C.c_int32 * 4)()
     check(lib.unet_postprocess_counters(counters.data_ptr(), host, _stream()), "postprocess_counters")
     return int(host[0]), int(host[1])
+
+
+# ---------------------------------------------------------------------------------------------- border distance and weight map (csrc/edt.hip)
+
+EDT_MAX_SIDE = 8192          # 2 * 8191^2 < 2^31: the squared distance fits int32
+EDT_NO_BORDER = 2 ** 31 - 1  # the squared distance of every pixel of an image without a border
+
+
+def check_edt_shape(what: str, shape):
+    """[B, H, W] with B >= 1 and 1 <= H, W <= 8192: refused from the shape alone"""
+    if len(shape) != 3 or any(int(v) < 1 for v in shape):
+        raise ValueError(f"{what}: expected a non-empty [B, H, W] batch of masks, got shape {tuple(shape)}")
+    if int(shape[1]) > EDT_MAX_SIDE or int(shape[2]) > EDT_MAX_SIDE:
+        raise ValueError(f"{what}: {int(shape[1])} x {int(shape[2])} px exceeds {EDT_MAX_SIDE} px a side (the squared distance is int32)")
+    if int(shape[0]) > 65535:
+        raise ValueError(f"{what}: at most 65535 masks per call, got {int(shape[0])}")
+
+
+def _edt_exclude(what: str, exclude) -> int:
+    if exclude is None:
+        return -1
+    if isinstance(exclude, bool) or not isinstance(exclude, int) or not 0 <= exclude < 2 ** 31:
+        raise ValueError(f"{what}: exclude must be None or a class id >= 0, got {exclude!r}")
+    return exclude
+
+
+def edt_workspace(B: int, H: int, W: int) -> int:
+    """bytes of the intermediate of border_edt"""
+    check_edt_shape("edt_workspace", (B, H, W))
+    return int(lib.unet_edt_workspace(B, H, W))
+
+
+def border_edt(mask: torch.Tensor, d2: torch.Tensor, ws: torch.Tensor, exclude=None):
+    """d2 int32 [B, H, W] = squared Euclidean distance to the nearest border pixel of the same image (EDT_NO_BORDER where an image has
+    none); mask uint8 or int64 [B, H, W]; ws: any tensor of at least edt_workspace(B, H, W) bytes (unet_hip.h has the rules)"""
+    check_edt_shape("border_edt", getattr(mask, "shape", ()))
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.int64):
+        raise ValueError(f"border_edt: mask must be a uint8 or int64 tensor, got {getattr(mask, 'dtype', type(mask))}")
+    if not mask.is_cuda or not mask.is_contiguous():
+        raise ValueError("border_edt: mask must be a contiguous tensor on the GPU")
+    _pp_tensor("border_edt", "d2", d2, torch.int32)
+    if tuple(d2.shape) != tuple(mask.shape) and d2.numel() != mask.numel():
+        raise ValueError(f"border_edt: d2 holds {d2.numel()} elements, the masks {mask.numel()}")
+    B, H, W = (int(v) for v in mask.shape)
+    need = edt_workspace(B, H, W)
+    if not isinstance(ws, torch.Tensor) or not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < need:
+        raise ValueError(f"border_edt: the workspace must be a contiguous GPU tensor of at least {need} bytes")
+    if d2.device != mask.device or ws.device != mask.device:
+        raise ValueError("border_edt: mask, d2 and the workspace must live on one device")
+    check(lib.unet_border_edt(mask.data_ptr(), int(mask.dtype == torch.int64), B, H, W, _edt_exclude("border_edt", exclude), d2.data_ptr(),
+                              ws.data_ptr(), _stream()), "border_edt")
+
+
+def border_weight(d2: torch.Tensor, target: torch.Tensor, class_w, n_classes: int, w0: float, sigma: float, pw: torch.Tensor):
+    """pw float32 [P] = class_w[y] + w0 * exp(-d2 / (2 sigma^2)); class_w float32 [n_classes] or None (ones); a target outside
+    [0, n_classes) gives 0, d2 == EDT_NO_BORDER a border term of exactly 0"""
+    if not w0 >= 0 or not sigma > 0:
+        raise ValueError(f"border_weight: needs w0 >= 0 and sigma > 0, got {w0!r} and {sigma!r}")
+    if isinstance(n_classes, bool) or not isinstance(n_classes, int) or n_classes < 1:
+        raise ValueError(f"border_weight: n_classes must be an int >= 1, got {n_classes!r}")
+    _pp_tensor("border_weight", "d2", d2, torch.int32)
+    P = d2.numel()
+    _pp_tensor("border_weight", "target", target, torch.int64)
+    _pp_tensor("border_weight", "pw", pw, torch.float32)
+    if P < 1 or target.numel() != P or pw.numel() != P:
+        raise ValueError(f"border_weight: d2, target and pw must hold the same number of pixels, got {P}, {target.numel()}, {pw.numel()}")
+    if class_w is not None:
+        _pp_tensor("border_weight", "class_w", class_w, torch.float32, numel=n_classes)
+    if any(t is not None and t.device != d2.device for t in (target, pw, class_w)):
+        raise ValueError("border_weight: every tensor must live on one device")
+    check(lib.unet_border_weight(d2.data_ptr(), target.data_ptr(), _p(class_w), n_classes, float(w0), float(sigma), P, pw.data_ptr(), _stream()),
+          "border_weight")

@@ -29,6 +29,7 @@ class TrainStep:
         self.focal_gamma: Optional[float] = None    # FocalLossFlat(gamma) instead of the weighted cross-entropy (params_and_main.py:87-89)
         self.dice = None        # a DiceLoss instead of the weighted cross-entropy (params_and_main.py:16): its smooth / reduction / square_in_union
         self.combined = None    # a CombinedLoss (focal + alpha * Dice) instead: its gamma / alpha / smooth / reduction / square_in_union
+        self.border = None      # a BorderWeightedCrossEntropy: the cross-entropy with the border weight map of the step's masks (its w0 / sigma / exclude)
         self.use_graph = use_graph and world == 1
         if self.use_graph:
             from .modules import SelfAttention
@@ -62,7 +63,8 @@ class TrainStep:
         if self._graph is None:
             if self._calls < 2:                     # eager warm-up: allocates every persistent buffer / workspace
                 self._calls += 1
-                loss = m.forward_loss_backward(x, y, self.weights, grad_scale=1.0, reg_kind=self.reg_kind, reg_beta=self.reg_beta, focal_gamma=self.focal_gamma, dice=self.dice, combined=self.combined)
+                loss = m.forward_loss_backward(x, y, self.weights, grad_scale=1.0, reg_kind=self.reg_kind, reg_beta=self.reg_beta, focal_gamma=self.focal_gamma, dice=self.dice, combined=self.combined,
+                                               border=self.border)
                 opt.step()
                 return loss
             self._xs = x.to(m._device, torch.float32).clone()
@@ -72,7 +74,8 @@ class TrainStep:
             self._graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._graph):
                 self._loss = m.forward_loss_backward(self._xs, self._ys, self.weights, grad_scale=1.0, reg_kind=self.reg_kind,
-                                                     reg_beta=self.reg_beta, focal_gamma=self.focal_gamma, dice=self.dice, combined=self.combined)
+                                                     reg_beta=self.reg_beta, focal_gamma=self.focal_gamma, dice=self.dice, combined=self.combined,
+                                                     border=self.border)
                 opt.step_from_device_hyper()
             # (the capture itself does not execute the step)
         self._xs.copy_(x, non_blocking=True)
@@ -92,7 +95,7 @@ class TrainStep:
         if self.reducer is not None:
             self.reducer.reset()
         loss = self.model.forward_loss_backward(x, y, self.weights, grad_scale=1.0, reg_kind=self.reg_kind, reg_beta=self.reg_beta,
-                                                world=self.world, focal_gamma=self.focal_gamma, dice=self.dice, combined=self.combined)
+                                                world=self.world, focal_gamma=self.focal_gamma, dice=self.dice, combined=self.combined, border=self.border)
         if self.reducer is not None:
             ev = self.comm_events
             if ev is not None:
