@@ -194,7 +194,7 @@ def test_not_implemented_refusals():
         with pytest.raises(NotImplementedError, match="per-channel mask_value"):
             cls(border_mode=0, mask_value=[1, 2])
         t = cls(interpolation=0, border_mode=0, value=0.5, mask_value=3)
-        assert t.modes() == (0, 0, 0.5, 3.0) and t.interpolating and isinstance(t, A._Geometric) and isinstance(t, A._NEW_GEOMETRIC)
+        assert t.modes() == (0, 0, 0.5, 3.0) and t.interpolating and isinstance(t, A._Geometric) and A._device_geometric(t)
     with pytest.raises(NotImplementedError, match="ShiftScaleRotate"):
         A.ElasticTransform(alpha_affine=50)
     A.ElasticTransform(alpha_affine=0), A.ElasticTransform(alpha_affine=None)

@@ -161,6 +161,34 @@ def test_identities_are_exact():
     assert torch.equal(out, xs)
 
 
+def test_a_translation_is_the_same_bits_through_the_affine_and_the_field_warp():
+    """Two entry points, one sampler (csrc/warp_sample.h): a pure translation through warp_affine[_mask] and through warp_field[_mask]
+    (optical with k = 0 and shift (dx, dy), all images fired, identity pre-map) gives the same bits.  Both paths form x + dx in fp64 from
+    exactly representable operands -- on the optical path (x - c) * 0 = +-0 -- and share the sampler from there on.  The shifts: a
+    fractional one, one far outside the image, an exact rounding tie.  (No D4 pre-maps here: a flipped sample uses the weights 1 - fx and
+    another summation order, so it is not bit-equal.)"""
+    shifts = np.array([(2.25, -3.5), (-0.75, 100.125), (0.5, 0.5)], np.float32)
+    maps = np.array([(1, 0, dx, 0, 1, dy) for dx, dy in shifts], np.float32)
+    optical = np.concatenate([np.zeros((3, 1), np.float32), shifts], axis=1)
+    g = torch.Generator().manual_seed(12)
+    for shape in ((3, 3, 40, 72), (3, 1, 1, 9)):
+        n, _, H, W = shape
+        x = torch.randn(shape, generator=g).cuda()
+        masks = (torch.randint(-5, 9, (n, H, W), generator=g).cuda(), torch.randn(n, H, W, generator=g).cuda())
+        for border in BORDERS:
+            for interp in (0, 1):
+                a, f = torch.empty_like(x), torch.empty_like(x)
+                ops.warp_affine(x, a, maps, interp, border, 0.375)
+                ops.warp_field(x, f, "optical", optical, [True] * n, None, interp, border, 0.375)
+                assert torch.equal(a.view(torch.int32), f.view(torch.int32)) and not torch.equal(a, x), (shape, border, interp)
+            for m in masks:
+                a, f = torch.empty_like(m), torch.empty_like(m)
+                ops.warp_affine_mask(m, a, maps, border, 5)
+                ops.warp_field_mask(m, f, "optical", optical, [True] * n, None, border, 5)
+                bits = torch.int64 if m.dtype == torch.int64 else torch.int32
+                assert torch.equal(a.view(bits), f.view(bits)) and not torch.equal(a, m), (shape, border, m.dtype)
+
+
 @pytest.mark.parametrize("field", ["elastic", "grid", "optical"])
 def test_d4_in_front_of_a_field_transform_is_one_launch_and_the_same_bits(field):
     """[flips, Transpose, RandomRotate90, field] is ONE segment; it equals the torch permutations followed by the field transform alone"""

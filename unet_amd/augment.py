@@ -233,13 +233,8 @@ class _Field(_Warp):
         fired = [prm is not None for prm in prms]
         params = self.field_params(prms, H, W, img.device)
         interp, border, fill, mask_fill = self.modes()
-        out = torch.empty_like(img, memory_format=torch.contiguous_format)
-        ops.warp_field(img.contiguous(), out, self.kind, params, fired, pre_maps, interp, border, fill)
-        if mask is None:
-            return out, None
-        mout = torch.empty_like(mask, memory_format=torch.contiguous_format)
-        ops.warp_field_mask(mask.contiguous(), mout, self.kind, params, fired, pre_maps, border, mask_fill)
-        return out, mout
+        return _warp_pair(img, mask, lambda src, dst: ops.warp_field(src, dst, self.kind, params, fired, pre_maps, interp, border, fill),
+                          lambda src, dst: ops.warp_field_mask(src, dst, self.kind, params, fired, pre_maps, border, mask_fill))
 
     def apply_params(self, img, mask, prm):
         x, y = self.warp_batch(img[None], None if mask is None else mask[None], [prm])
@@ -382,7 +377,9 @@ class OpticalDistortion(_Field):
         return np.array([(0.0, 0.0, 0.0) if prm is None else prm for prm in prms], dtype=np.float32).reshape(len(prms), 3)
 
 
-_NEW_GEOMETRIC = (RandomRotate90, Transpose, Rotate, ShiftScaleRotate, ElasticTransform, GridDistortion, OpticalDistortion)
+def _device_geometric(t) -> bool:
+    """a geometric transform that is not one of the two flips: it exists as a device warp only"""
+    return isinstance(t, _Geometric) and not isinstance(t, (HorizontalFlip, VerticalFlip))
 
 
 def inverse_map(forward: np.ndarray) -> np.ndarray:
@@ -394,16 +391,23 @@ def inverse_map(forward: np.ndarray) -> np.ndarray:
     return inv.astype(np.float32)
 
 
+def _warp_pair(img: torch.Tensor, mask, warp_image, warp_mask):
+    """image batch [n, C, H, W] fp32 and mask batch [n, H, W] (or None) warped into new tensors by warp_image(src, dst) and, when there
+    is a mask, warp_mask(src, dst)"""
+    out = torch.empty_like(img, memory_format=torch.contiguous_format)
+    warp_image(img.contiguous(), out)
+    if mask is None:
+        return out, None
+    mout = torch.empty_like(mask, memory_format=torch.contiguous_format)
+    warp_mask(mask.contiguous(), mout)
+    return out, mout
+
+
 def _warp(img: torch.Tensor, mask, inv_maps: np.ndarray, interp: int, border: int, fill: float, mask_fill: float):
     """image batch [n, C, H, W] fp32 and mask batch [n, H, W] (or None) warped by inv_maps [n, 6] into new tensors"""
     from . import ops
-    out = torch.empty_like(img)
-    ops.warp_affine(img.contiguous(), out, inv_maps, interp, border, fill)
-    if mask is None:
-        return out, None
-    mout = torch.empty_like(mask)
-    ops.warp_affine_mask(mask.contiguous(), mout, inv_maps, border, mask_fill)
-    return out, mout
+    return _warp_pair(img, mask, lambda src, dst: ops.warp_affine(src, dst, inv_maps, interp, border, fill),
+                      lambda src, dst: ops.warp_affine_mask(src, dst, inv_maps, border, mask_fill))
 
 
 class _Pointwise(_Transform):
@@ -743,7 +747,7 @@ class BatchAugment:
 
     def __call__(self, xb: torch.Tensor, yb: torch.Tensor):
         """augments xb [B, C, H, W] / yb [B, H, W] in place and returns them"""
-        if any(isinstance(t, _NEW_GEOMETRIC) for t in self.aug.transforms) or (xb.is_cuda and not self.flips_only):
+        if any(_device_geometric(t) for t in self.aug.transforms) or (xb.is_cuda and not self.flips_only):
             return self._batched(xb, yb)
         B = xb.shape[0]
         n_transform = math.ceil(B * self.n)
@@ -897,19 +901,11 @@ class BatchAugment:
 
     def _flip_flags(self, B: int) -> list:
         """the random draws of ``__call__`` in its order, reduced to (mirror along the width, mirror along the height) per image"""
-        n_transform = math.ceil(B * self.n)
-        flags = [(False, False)] * B
-        for i in list(range(B))[:n_transform - B]:
-            h = v = False
-            if self.g.random() < self.aug.p:           # Compose.__call__: `if g.random() >= self.p: return`
-                for t in self.aug.transforms:          # _Transform.__call__: `if g.random() < self.p: apply`
-                    if self.g.random() < t.p:
-                        if type(t) is HorizontalFlip:
-                            h = not h
-                        else:
-                            v = not v
-            flags[i] = (h, v)
-        return flags
+        fired = self.draw(B, 0, 0)                     # flips draw no parameters: exactly the fire draws of ``__call__``
+
+        def odd(i, flip):
+            return sum(type(t) is flip and (i, k) in fired for k, t in enumerate(self.aug.transforms)) % 2 == 1
+        return [(odd(i, HorizontalFlip), odd(i, VerticalFlip)) for i in range(B)]
 
 
 def default_pipeline() -> Compose:

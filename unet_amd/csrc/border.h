@@ -1,4 +1,5 @@
-// cv2.borderInterpolate on the device: shared by the affine warps (warp.hip) and the separable blur (pixel_aug.hip)
+// cv2.borderInterpolate on the device: shared by the sampler of the affine and field warps (warp_sample.h: warp.hip, warp_field.hip), the
+// elastic-field filter (warp_field.hip) and the separable blur (pixel_aug.hip)
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -5,9 +5,10 @@
 // the displacement of the launch's kind -- a dense field [n, 2, H, W] in device memory (8 bytes per pixel next to the 32 the image
 // moves at C = 4), or evaluated per pixel from the image's descriptor in the kernel arguments (grid: per-axis node values with the
 // linspace between them; optical: k, dx, dy) -- and zero for an image that did not fire.  pre_j is the 2 x 3 inverse map of the D4
-// transforms that share the segment: a permutation of the grid, applied to the tap indices (TapMap below).  One thread per output
-// pixel, x fastest; coordinates in fp64 clamped to +-2^24, taps and bilinear weights computed once for all planes, exactly as
-// csrc/warp.hip does.  Every tap index is mapped into the image by border_index or replaced by fill, and a checked D4 map keeps it
+// transforms that share the segment: a permutation of the grid, applied to the tap indices (TapMap of warp_sample.h).  One thread per
+// output pixel, x fastest; coordinates in fp64 clamped to +-2^24, then the sampler of csrc/warp_sample.h, the one csrc/warp.hip uses:
+// taps and bilinear weights computed once for all planes.  Every tap index is mapped into the image by border_index or replaced by
+// fill, and a checked D4 map keeps it
 // there, so no field value -- NaN and infinity included -- reaches memory outside src.
 //
 // elastic_rows_kernel / elastic_cols_kernel, the displacement field of ElasticTransform: uniform noise in (-1, 1) smoothed by a separable
@@ -20,11 +21,8 @@
 // uniform index (scalar loads).
 //
 // No atomics, no device allocation, no host wait; the only stores are each thread's own output elements.
-#include <cmath>
-
-#include "border.h"
-#include "common.h"
 #include "philox.h"
+#include "warp_sample.h"
 
 using namespace unet;
 
@@ -38,11 +36,6 @@ struct Elastic {              // 2.8 KB
     unet_elastic_image im[UNET_ELASTIC_MAX_IMAGES];
     float taps[UNET_ELASTIC_MAX_KSIZE];
 };
-
-__device__ __forceinline__ float tap(const float* __restrict__ plane, size_t o, bool ok, float fill) {
-    const float v = plane[o];
-    return ok ? v : fill;
-}
 
 // entry i of np.linspace over the cell of i: cells of `step` entries (the last one clipped at N), cell c from nodes[c] to nodes[c + 1],
 // endpoint included; a cell of one entry gets its first node
@@ -79,19 +72,7 @@ __device__ __forceinline__ void src_coords(const unet_field_image& im, const flo
     sy = fmin(fmax(py, -LIM), LIM);
 }
 
-// The pre-map of an image is a D4 map of the H x W grid (load_images checks it): integer entries, a permutation of the grid.  Sampling the
-// permuted image at s is sampling the image at the permuted taps of s with the same weights and the same border rule, so the map is
-// applied to the tap indices -- exact, and bit for bit what permuting first would give.
-struct TapMap {
-    int a, b, c, d, e, f, W;
-    __device__ __forceinline__ explicit TapMap(const float* m, int W_)
-        : a((int)m[0]), b((int)m[1]), c((int)m[2]), d((int)m[3]), e((int)m[4]), f((int)m[5]), W(W_) {}
-    // the offset in a plane of tap (ix, iy), both inside the grid
-    __device__ __forceinline__ size_t operator()(int ix, int iy) const {
-        return (size_t)(d * ix + e * iy + f) * W + (size_t)(a * ix + b * iy + c);
-    }
-};
-
+// pre = the image's D4 pre-map (load_images checks it), applied to the tap indices: TapMap of warp_sample.h
 template <int KIND, int BORDER, int INTERP>
 __global__ __launch_bounds__(256) void warp_field_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                          const float* __restrict__ field, int C, int H, int W, int step_x, int step_y,
@@ -100,46 +81,14 @@ __global__ __launch_bounds__(256) void warp_field_kernel(const float* __restrict
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= HW) return;
     const int j = blockIdx.y;
-    const int y = (int)(p / W), x = (int)(p - (long long)y * W);
+    int x, y;
+    pixel_xy(p, W, x, y);
     double sx, sy;
     src_coords<KIND>(images.im[j], KIND == UNET_FIELD_DENSE ? field + (size_t)j * 2 * HW : nullptr, p, HW, x, y, H, W, step_x, step_y, sx, sy);
     const TapMap at(images.im[j].pre, W);
-    const float* s = src + (size_t)j * C * HW;
-    float* d = dst + (size_t)j * C * HW + p;
-    if (INTERP == 0) {
-        const int ix = border_index<BORDER>((int)floor(sx + 0.5), W), iy = border_index<BORDER>((int)floor(sy + 0.5), H);
-        const bool ok = ix >= 0 && iy >= 0;
-        const size_t o = ok ? at(ix, iy) : 0;
-#pragma unroll 4
-        for (int c = 0; c < C; ++c) d[(size_t)c * HW] = tap(s + (size_t)c * HW, o, ok, fill);
-        return;
-    }
-    const double fx0 = floor(sx), fy0 = floor(sy);
-    const float fx = (float)(sx - fx0), fy = (float)(sy - fy0);           // fp32 weights
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int ix0 = border_index<BORDER>(x0, W), ix1 = border_index<BORDER>(x0 + 1, W);
-    const int iy0 = border_index<BORDER>(y0, H), iy1 = border_index<BORDER>(y0 + 1, H);
-    if (fx == 0.0f && fy == 0.0f) {                    // on a grid point (an unfired image, a zero field): an exact copy of the tap
-        const bool ok = ix0 >= 0 && iy0 >= 0;
-        const size_t o = ok ? at(ix0, iy0) : 0;
-#pragma unroll 4
-        for (int c = 0; c < C; ++c) d[(size_t)c * HW] = tap(s + (size_t)c * HW, o, ok, fill);
-        return;
-    }
-    const bool ok00 = ix0 >= 0 && iy0 >= 0, ok01 = ix1 >= 0 && iy0 >= 0, ok10 = ix0 >= 0 && iy1 >= 0, ok11 = ix1 >= 0 && iy1 >= 0;
-    const size_t o00 = ok00 ? at(ix0, iy0) : 0, o01 = ok01 ? at(ix1, iy0) : 0;
-    const size_t o10 = ok10 ? at(ix0, iy1) : 0, o11 = ok11 ? at(ix1, iy1) : 0;
-    const float w00 = (1.0f - fx) * (1.0f - fy), w01 = fx * (1.0f - fy), w10 = (1.0f - fx) * fy, w11 = fx * fy;
-#pragma unroll 4
-    for (int c = 0; c < C; ++c) {
-        const float* sc = s + (size_t)c * HW;
-        const float v00 = tap(sc, o00, ok00, fill), v01 = tap(sc, o01, ok01, fill);
-        const float v10 = tap(sc, o10, ok10, fill), v11 = tap(sc, o11, ok11, fill);
-        d[(size_t)c * HW] = w00 * v00 + w01 * v01 + w10 * v10 + w11 * v11;
-    }
+    sample_planes<BORDER, INTERP>(src + (size_t)j * C * HW, dst + (size_t)j * C * HW + p, C, HW, H, W, sx, sy, at, fill);
 }
 
-// masks: nearest neighbour, floor(s + 0.5), whatever the image interpolation
 template <typename T, int KIND, int BORDER>
 __global__ __launch_bounds__(256) void warp_field_mask_kernel(const T* __restrict__ src, T* __restrict__ dst, const float* __restrict__ field,
                                                               int H, int W, int step_x, int step_y, Images images, T fill) {
@@ -147,12 +96,12 @@ __global__ __launch_bounds__(256) void warp_field_mask_kernel(const T* __restric
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= HW) return;
     const int j = blockIdx.y;
-    const int y = (int)(p / W), x = (int)(p - (long long)y * W);
+    int x, y;
+    pixel_xy(p, W, x, y);
     double sx, sy;
     src_coords<KIND>(images.im[j], KIND == UNET_FIELD_DENSE ? field + (size_t)j * 2 * HW : nullptr, p, HW, x, y, H, W, step_x, step_y, sx, sy);
-    const int ix = border_index<BORDER>((int)floor(sx + 0.5), W), iy = border_index<BORDER>((int)floor(sy + 0.5), H);
     const TapMap at(images.im[j].pre, W);
-    dst[(size_t)j * HW + p] = ix >= 0 && iy >= 0 ? src[(size_t)j * HW + at(ix, iy)] : fill;
+    sample_mask<T, BORDER>(src, dst, j, HW, p, H, W, sx, sy, at, fill);
 }
 
 // ----------------------------------------------------------------------------------------------------------- the elastic field
@@ -245,19 +194,6 @@ __global__ __launch_bounds__(256) void elastic_cols_kernel(const float* __restri
         if (rg + CT_G * i < th) d[(size_t)(rg + CT_G * i) * W] = im.alpha * acc[i];
 }
 
-// H, W <= 2^24 keeps every index expression of border_index inside int
-bool sizes_ok(int n, int nmax, int H, int W) {
-    return n >= 1 && n <= nmax && H > 0 && W > 0 && H <= (1 << 24) && W <= (1 << 24) && (long long)H * W <= 0x7fffffffLL;
-}
-
-bool known_border(int b) { return b == B_CONSTANT || b == B_REPLICATE || b == B_REFLECT || b == B_REFLECT101; }
-
-bool all_finite(const float* v, int n) {
-    for (int k = 0; k < n; ++k)
-        if (!std::isfinite(v[k])) return false;
-    return true;
-}
-
 // m maps the grid [0, W) x [0, H) onto itself as a flip, a transposition or a product of them: each row has one entry +-1 on its own
 // axis (or, on a square grid, on the other one), offset 0 for +1 and N - 1 for -1
 bool d4_map(const float* m, int H, int W) {
@@ -303,14 +239,6 @@ const char* load_images(const unet_field_image* host, int n, int kind, const flo
 
 #define ST ((hipStream_t)stream)
 
-#define BORDER_DISPATCH(border, CALL)                                 \
-    switch (border) {                                                 \
-        case B_CONSTANT: { constexpr int BM = B_CONSTANT; CALL; break; }     \
-        case B_REPLICATE: { constexpr int BM = B_REPLICATE; CALL; break; }   \
-        case B_REFLECT: { constexpr int BM = B_REFLECT; CALL; break; }       \
-        default: { constexpr int BM = B_REFLECT101; CALL; break; }           \
-    }
-
 #define KIND_DISPATCH(kind, CALL)                                              \
     switch (kind) {                                                            \
         case UNET_FIELD_DENSE: { constexpr int KD = UNET_FIELD_DENSE; CALL; break; }   \
@@ -320,13 +248,8 @@ const char* load_images(const unet_field_image* host, int n, int kind, const flo
 
 extern "C" int unet_warp_field(const float* src, float* dst, int n, int C, int H, int W, int kind, const unet_field_image* images_host,
                                const float* field, int grid_step_x, int grid_step_y, int interp, int border, float fill, void* stream) {
-    UNET_CHECK_ARG(src && dst && images_host, "warp_field: null pointer");
-    UNET_CHECK_ARG(src != dst && field != dst, "warp_field: src == dst or field == dst (the warp is out of place)");
-    UNET_CHECK_ARG(sizes_ok(n, UNET_FIELD_MAX_IMAGES, H, W) && C > 0, "warp_field: bad sizes n=%d C=%d H=%d W=%d (1..%d images per call)",
-                   n, C, H, W, UNET_FIELD_MAX_IMAGES);
-    UNET_CHECK_ARG(interp == 0 || interp == 1, "warp_field: unknown interpolation %d (0 nearest, 1 bilinear)", interp);
-    UNET_CHECK_ARG(known_border(border), "warp_field: unknown border mode %d (0 constant, 1 replicate, 2 reflect, 4 reflect-101)", border);
-    UNET_CHECK_ARG(std::isfinite(fill), "warp_field: non-finite fill value");
+    if (const int e = check_image_args("warp_field", src, dst, images_host, field, true, n, UNET_FIELD_MAX_IMAGES, C, H, W, interp, border, fill))
+        return e;
     Images images;
     const char* err = load_images(images_host, n, kind, field, H, W, grid_step_x, grid_step_y, images);
     UNET_CHECK_ARG(err == nullptr, "warp_field: %s", err);
@@ -346,26 +269,15 @@ extern "C" int unet_warp_field(const float* src, float* dst, int n, int C, int H
 
 extern "C" int unet_warp_field_mask(const void* src, void* dst, int dst_f32, int n, int H, int W, int kind, const unet_field_image* images_host,
                                     const float* field, int grid_step_x, int grid_step_y, int border, double fill, void* stream) {
-    UNET_CHECK_ARG(src && dst && images_host, "warp_field_mask: null pointer");
-    UNET_CHECK_ARG(src != dst && (const void*)field != dst, "warp_field_mask: src == dst or field == dst (the warp is out of place)");
-    UNET_CHECK_ARG(dst_f32 == 0 || dst_f32 == 1, "warp_field_mask: dst_f32 must be 0 (int64) or 1 (fp32)");
-    UNET_CHECK_ARG(sizes_ok(n, UNET_FIELD_MAX_IMAGES, H, W), "warp_field_mask: bad sizes n=%d H=%d W=%d (1..%d masks per call)", n, H, W,
-                   UNET_FIELD_MAX_IMAGES);
-    UNET_CHECK_ARG(known_border(border), "warp_field_mask: unknown border mode %d (0 constant, 1 replicate, 2 reflect, 4 reflect-101)", border);
-    UNET_CHECK_ARG(std::isfinite(fill) && (dst_f32 || fabs(fill) < 9.2e18), "warp_field_mask: fill value %g is not finite / not an int64", fill);
+    if (const int e = check_mask_args("warp_field_mask", src, dst, images_host, field, true, dst_f32, n, UNET_FIELD_MAX_IMAGES, H, W, border, fill))
+        return e;
     Images images;
     const char* err = load_images(images_host, n, kind, field, H, W, grid_step_x, grid_step_y, images);
     UNET_CHECK_ARG(err == nullptr, "warp_field_mask: %s", err);
     const dim3 grid(cdiv((long long)H * W, 256), n);
-    if (dst_f32) {
-        KIND_DISPATCH(kind, BORDER_DISPATCH(border, hipLaunchKernelGGL((warp_field_mask_kernel<float, KD, BM>), grid, dim3(256), 0, ST,
-                                                                       (const float*)src, (float*)dst, field, H, W, grid_step_x, grid_step_y,
-                                                                       images, (float)fill)));
-    } else {
-        KIND_DISPATCH(kind, BORDER_DISPATCH(border, hipLaunchKernelGGL((warp_field_mask_kernel<long long, KD, BM>), grid, dim3(256), 0, ST,
-                                                                       (const long long*)src, (long long*)dst, field, H, W, grid_step_x,
-                                                                       grid_step_y, images, (long long)fill)));
-    }
+    MASK_DISPATCH(dst_f32, KIND_DISPATCH(kind, BORDER_DISPATCH(border, hipLaunchKernelGGL((warp_field_mask_kernel<MT, KD, BM>), grid, dim3(256), 0,
+                                                                                          ST, (const MT*)src, (MT*)dst, field, H, W, grid_step_x,
+                                                                                          grid_step_y, images, (MT)fill))));
     UNET_CHECK_LAUNCH();
     return UNET_OK;
 }

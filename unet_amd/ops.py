@@ -7,6 +7,7 @@ physical channel stride ``cs`` (this is how ``torch.cat`` disappears).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -1020,7 +1021,27 @@ def dice_counts(pred: torch.Tensor, targ: torch.Tensor, n_cls: int, counts: torc
 
 # ------------------------------------------------------------------ geometric augmentation (csrc/warp.hip: unet_warp_affine[_mask])
 
+WARP_MAX_IMAGES = 64       # warp.hip MAXMAPS
+
+
+def _chunks(n: int, limit: int):
+    """(at, m) for every call of a kernel that takes at most `limit` images: images [at, at + m) of n"""
+    for at in range(0, n, limit):
+        yield at, min(limit, n - at)
+
+
+def _image_ptr(t: torch.Tensor, at: int) -> int:
+    """the address of image `at` of the contiguous batch t"""
+    return t.data_ptr() + at * math.prod(t.shape[1:]) * t.element_size()
+
+
+def _struct_ptr(array, at: int):
+    """a pointer to element `at` of a ctypes array"""
+    return C.cast(C.byref(array, at * C.sizeof(array._type_)), C.POINTER(array._type_))
+
+
 def _warp_args(what: str, src: torch.Tensor, dst: torch.Tensor, inv_maps, dims: int):
+    """the checked maps, fp32 [n, 6], of a warp of images (dims 4: [n, C, H, W] fp32) or masks (dims 3: [n, H, W] int64 or fp32)"""
     if not (src.is_cuda and dst.is_cuda):
         raise RuntimeError(f"{what}: the warp runs on the device only (HIP, no CPU fallback); got {src.device} / {dst.device} tensors")
     assert src.dim() == dims and src.is_contiguous() and dst.is_contiguous() and src.shape == dst.shape and src.dtype == dst.dtype, \
@@ -1028,6 +1049,7 @@ def _warp_args(what: str, src: torch.Tensor, dst: torch.Tensor, inv_maps, dims: 
     import numpy as np
     maps = np.ascontiguousarray(inv_maps, dtype=np.float32).reshape(-1, 6)
     assert maps.shape[0] == src.shape[0], (what, maps.shape, src.shape)
+    assert src.dtype in ((torch.float32,) if dims == 4 else (torch.int64, torch.float32)), src.dtype
     return maps
 
 
@@ -1035,26 +1057,19 @@ def warp_affine(src: torch.Tensor, dst: torch.Tensor, inv_maps, interp: int, bor
     """dst[j] = src[j] sampled at inv_maps[j] (2 x 3 per image, output -> source) with interp 0 nearest / 1 bilinear and a cv2 border
     code; src / dst [n, C, H, W] fp32 on the device, out of place"""
     maps = _warp_args("warp_affine", src, dst, inv_maps, 4)
-    assert src.dtype == torch.float32, src.dtype
     n, Cc, H, W = src.shape
-    per = Cc * H * W
-    for at in range(0, n, 64):
-        m = min(64, n - at)
-        check(lib.unet_warp_affine(src.data_ptr() + at * per * 4, dst.data_ptr() + at * per * 4, m, Cc, H, W,
-                                   maps[at:at + m].ctypes.data_as(L.c_float_p), int(interp), int(border), float(fill), _stream()), "warp_affine")
+    for at, m in _chunks(n, WARP_MAX_IMAGES):
+        check(lib.unet_warp_affine(_image_ptr(src, at), _image_ptr(dst, at), m, Cc, H, W, maps[at:at + m].ctypes.data_as(L.c_float_p),
+                                   int(interp), int(border), float(fill), _stream()), "warp_affine")
 
 
 def warp_affine_mask(src: torch.Tensor, dst: torch.Tensor, inv_maps, border: int, fill: float = 0.0):
     """the nearest-neighbour warp of masks [n, H, W] int64 (classification) or fp32 (regression targets), same maps as warp_affine"""
     maps = _warp_args("warp_affine_mask", src, dst, inv_maps, 3)
-    assert src.dtype in (torch.int64, torch.float32), src.dtype
     n, H, W = src.shape
-    es = src.element_size()
-    for at in range(0, n, 64):
-        m = min(64, n - at)
-        check(lib.unet_warp_affine_mask(src.data_ptr() + at * H * W * es, dst.data_ptr() + at * H * W * es, int(src.dtype == torch.float32),
-                                        m, H, W, maps[at:at + m].ctypes.data_as(L.c_float_p), int(border), float(fill), _stream()),
-              "warp_affine_mask")
+    for at, m in _chunks(n, WARP_MAX_IMAGES):
+        check(lib.unet_warp_affine_mask(_image_ptr(src, at), _image_ptr(dst, at), int(src.dtype == torch.float32), m, H, W,
+                                        maps[at:at + m].ctypes.data_as(L.c_float_p), int(border), float(fill), _stream()), "warp_affine_mask")
 
 
 # ------------------------------------------------------------------ non-rigid augmentation (csrc/warp_field.hip)
@@ -1063,7 +1078,8 @@ FIELD_KINDS = {"dense": L.FIELD_DENSE, "grid": L.FIELD_GRID, "optical": L.FIELD_
 
 
 def _field_args(what: str, src: torch.Tensor, dst: torch.Tensor, kind: str, params, fired, pre_maps, dims: int):
-    """the checked arguments of a field warp: (kind code, descriptor array, field tensor or None, grid steps)"""
+    """the checked arguments of a field warp, as a function of the first image of a call: at -> (kind code, descriptors, field or None,
+    grid step x, grid step y), the run of arguments unet_warp_field and unet_warp_field_mask share"""
     import numpy as np
     if kind not in FIELD_KINDS:
         raise ValueError(f"{what}: unknown kind {kind!r} (dense, grid, optical)")
@@ -1098,7 +1114,7 @@ def _field_args(what: str, src: torch.Tensor, dst: torch.Tensor, kind: str, para
         assert opt.shape == (n, 3), (what, opt.shape)
         for j in range(n):
             images[j].optical[:] = opt[j].tolist()
-    return FIELD_KINDS[kind], images, field, steps
+    return lambda at: (FIELD_KINDS[kind], _struct_ptr(images, at), None if field is None else _image_ptr(field, at), *steps)
 
 
 def warp_field(src: torch.Tensor, dst: torch.Tensor, kind: str, params, fired, pre_maps=None, interp: int = 1, border: int = 4,
@@ -1107,30 +1123,20 @@ def warp_field(src: torch.Tensor, dst: torch.Tensor, kind: str, params, fired, p
     on the device, "grid" with params (step_x, step_y, nodes [n, 2, 17]) or "optical" with params [n, 3] = (k, dx, dy); d_j = 0 where
     fired[j] is false; pre_maps [n, 6]: D4 maps of the grid as augment.inverse_map gives them (None: identities).  src / dst [n, C, H, W] fp32 on the device, out of place; batches above 16
     images run in chunks"""
-    code, images, field, steps = _field_args("warp_field", src, dst, kind, params, fired, pre_maps, 4)
-    assert src.dtype == torch.float32, src.dtype
+    field_args = _field_args("warp_field", src, dst, kind, params, fired, pre_maps, 4)
     n, Cc, H, W = src.shape
-    per = Cc * H * W
-    for at in range(0, n, L.FIELD_MAX_IMAGES):
-        m = min(L.FIELD_MAX_IMAGES, n - at)
-        check(lib.unet_warp_field(src.data_ptr() + at * per * 4, dst.data_ptr() + at * per * 4, m, Cc, H, W, code,
-                                  C.cast(C.byref(images, at * C.sizeof(L.FieldImage)), C.POINTER(L.FieldImage)),
-                                  None if field is None else field.data_ptr() + at * 2 * H * W * 4, steps[0], steps[1], int(interp),
-                                  int(border), float(fill), _stream()), "warp_field")
+    for at, m in _chunks(n, L.FIELD_MAX_IMAGES):
+        check(lib.unet_warp_field(_image_ptr(src, at), _image_ptr(dst, at), m, Cc, H, W, *field_args(at), int(interp), int(border),
+                                  float(fill), _stream()), "warp_field")
 
 
 def warp_field_mask(src: torch.Tensor, dst: torch.Tensor, kind: str, params, fired, pre_maps=None, border: int = 4, fill: float = 0.0):
     """the nearest-neighbour field warp of masks [n, H, W] int64 or fp32, same arguments as warp_field"""
-    code, images, field, steps = _field_args("warp_field_mask", src, dst, kind, params, fired, pre_maps, 3)
-    assert src.dtype in (torch.int64, torch.float32), src.dtype
+    field_args = _field_args("warp_field_mask", src, dst, kind, params, fired, pre_maps, 3)
     n, H, W = src.shape
-    es = src.element_size()
-    for at in range(0, n, L.FIELD_MAX_IMAGES):
-        m = min(L.FIELD_MAX_IMAGES, n - at)
-        check(lib.unet_warp_field_mask(src.data_ptr() + at * H * W * es, dst.data_ptr() + at * H * W * es, int(src.dtype == torch.float32),
-                                       m, H, W, code, C.cast(C.byref(images, at * C.sizeof(L.FieldImage)), C.POINTER(L.FieldImage)),
-                                       None if field is None else field.data_ptr() + at * 2 * H * W * 4, steps[0], steps[1], int(border),
-                                       float(fill), _stream()), "warp_field_mask")
+    for at, m in _chunks(n, L.FIELD_MAX_IMAGES):
+        check(lib.unet_warp_field_mask(_image_ptr(src, at), _image_ptr(dst, at), int(src.dtype == torch.float32), m, H, W, *field_args(at),
+                                       int(border), float(fill), _stream()), "warp_field_mask")
 
 
 def elastic_field(field: torch.Tensor, workspace: torch.Tensor, keys, alpha, fired, same_dxdy: bool, taps):
@@ -1154,11 +1160,8 @@ def elastic_field(field: torch.Tensor, workspace: torch.Tensor, keys, alpha, fir
     images = (L.ElasticImage * n)()
     for j in range(n):
         images[j] = L.ElasticImage(int(keys[j, 0]) & 0xffffffff, int(keys[j, 1]) & 0xffffffff, float(alphas[j]), int(flags[j]), int(bool(same_dxdy)))
-    per = 2 * H * W * 4
-    for at in range(0, n, L.ELASTIC_MAX_IMAGES):
-        m = min(L.ELASTIC_MAX_IMAGES, n - at)
-        check(lib.unet_elastic_field(field.data_ptr() + at * per, workspace.data_ptr() + at * per, m, H, W,
-                                     C.cast(C.byref(images, at * C.sizeof(L.ElasticImage)), C.POINTER(L.ElasticImage)),
+    for at, m in _chunks(n, L.ELASTIC_MAX_IMAGES):
+        check(lib.unet_elastic_field(_image_ptr(field, at), _image_ptr(workspace, at), m, H, W, _struct_ptr(images, at),
                                      taps.ctypes.data_as(L.c_float_p), len(taps), _stream()), "elastic_field")
 
 
@@ -1286,12 +1289,9 @@ def blur_separable(src: torch.Tensor, dst: torch.Tensor, taps: list):
     tab = np.zeros((n, L.BLUR_MAX_KSIZE), dtype=np.float32)
     for j, t in enumerate(taps):
         tab[j, :len(t)] = t
-    per = Cc * H * W
-    for at in range(0, n, L.BLUR_MAX_IMAGES):
-        m = min(L.BLUR_MAX_IMAGES, n - at)
-        check(lib.unet_blur_separable(src.data_ptr() + at * per * 4, dst.data_ptr() + at * per * 4, m, Cc, H, W,
-                                      ks[at:at + m].ctypes.data_as(C.POINTER(C.c_int)), tab[at:at + m].ctypes.data_as(L.c_float_p), _stream()),
-              "blur_separable")
+    for at, m in _chunks(n, L.BLUR_MAX_IMAGES):
+        check(lib.unet_blur_separable(_image_ptr(src, at), _image_ptr(dst, at), m, Cc, H, W, ks[at:at + m].ctypes.data_as(C.POINTER(C.c_int)),
+                                      tab[at:at + m].ctypes.data_as(L.c_float_p), _stream()), "blur_separable")
 
 
 def mosaic_accumulate_windows(z: TS, table: torch.Tensor, first: int, n: int, origin, mosaic: torch.Tensor, count: torch.Tensor,
