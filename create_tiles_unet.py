@@ -59,9 +59,10 @@ def create_train_test_split(path, split=None, seed: Optional[int] = None):
 
 
 def split_raster(path_to_raster=None, path_to_mask=None, base_dir=".", patch_size=400, patch_overlap=0.20, split=None, max_empty=0.9,
-                 class_zero=False, seed: Optional[int] = None):
+                 class_zero=False, seed: Optional[int] = None, compress=None, predictor=1):
     """Cut a raster (and its mask) into patch_size tiles, drop tiles that are more than max_empty empty, write GeoTIFF tiles
-    with their own geotransform and split them into trai / vali / test."""
+    with their own geotransform and split them into trai / vali / test.  compress / predictor go straight to tiffio.write_tiff
+    ("lzw", 2: LZW tiles with horizontal differencing; the reader and the feed take them as they take uncompressed ones)."""
     if split is None:
         split = [0.7, 0.2, 0.1]
     base = Path(base_dir)
@@ -115,10 +116,10 @@ def split_raster(path_to_raster=None, path_to_mask=None, base_dir=".", patch_siz
             if mcrop.size == 0 or np.sum(mcrop != 0) < mcrop.size * (1 - max_empty):
                 continue
         tgt = (gt[0] + x * gt[1], gt[1], 0.0, gt[3] + y * gt[5], 0.0, gt[5])
-        write_tiff(base / "img_tiles" / f"{name}_{index}.tif", crop, geotransform=tgt, tags=meta["tags"])
+        write_tiff(base / "img_tiles" / f"{name}_{index}.tif", crop, geotransform=tgt, tags=meta["tags"], compress=compress, predictor=predictor)
         if mask is not None:
             md = mcrop[0] if mcrop.dtype.kind == "f" else mcrop[0].astype(np.uint8)
-            write_tiff(base / "mask_tiles" / f"{name}_{index}.tif", md, geotransform=tgt, tags=meta["tags"])
+            write_tiff(base / "mask_tiles" / f"{name}_{index}.tif", md, geotransform=tgt, tags=meta["tags"], compress=compress, predictor=predictor)
         kept += 1
     counts = create_train_test_split(base, split=split, seed=seed) if mask is not None else {"tiles": kept}
     return counts

@@ -695,6 +695,27 @@ int unet_border_weight(const int32_t* d2, const int64_t* target, const float* cl
  * Return the number of bytes written to dst (capacity cap), -1 on a malformed stream or overflow. */
 long long unet_tiff_lzw_decode(const unsigned char* src, long long n, unsigned char* dst, long long cap);      /* TIFF 6.0 LZW (compression 5) */
 long long unet_tiff_packbits_decode(const unsigned char* src, long long n, unsigned char* dst, long long cap); /* PackBits (compression 32773) */
+/* The LZW encoder of the writer (same file, host-side): one strip of n bytes -> dst, the number of bytes written, or -1 instead of writing
+ * past dst + cap.  The code stream is the one rule of DESIGN 3.16 (Clear first, early change, Clear when the next code would be 4094,
+ * EOI, zero padding); unet_tiff_lzw_cap(n) = (3 * (n + n / 3836 + 4) + 1) / 2 bytes always suffice. */
+long long unet_tiff_lzw_cap(long long n);
+long long unet_tiff_lzw_encode(const unsigned char* src, long long n, unsigned char* dst, long long cap);
+
+/* ---------------------------------------------------- GeoTIFF encoding on the device --
+ * csrc/tiff_encode.hip (unet_amd/tiffenc.py): LZW strips of a device image, byte for byte what unet_tiff_lzw_encode writes.
+ * The image is [P, H, W] samples of elem_size 1, 2 or 4 bytes; row_stride / plane_stride are in samples (W contiguous samples per row).
+ * Strips hold rows_per_strip rows (the last one of a plane fewer); strip k = p * strips_per_plane + s is strip s of plane p.
+ * unet_tiff_encode_strips: strips [first, first + count) -> scratch + j * slot_bytes for j = k - first, sizes[j] = encoded bytes.
+ *   predictor 2: horizontal differencing per sample modulo 2^bits, applied while the input is staged.  slot_bytes: a multiple of 4, at
+ *   least unet_tiff_lzw_cap(rows_per_strip * W * elem_size) -- the kernel never writes outside a slot; a slot that would overflow (it
+ *   cannot, by the capacity rule) reports sizes[j] = 0xFFFFFFFF.  One wavefront per strip; deterministic, no atomics.
+ * unet_tiff_compact_strips: out[offsets[j], offsets[j] + sizes[j]) = slot j, for count slots; offsets = exclusive prefix sum of sizes.
+ * Bad arguments return -1 before any launch. */
+int unet_tiff_encode_strips(const void* src, int elem_size, int P, int H, int W, long long row_stride, long long plane_stride,
+                            int rows_per_strip, int predictor, long long first, int count, unsigned char* scratch, long long slot_bytes,
+                            uint32_t* sizes, void* stream);
+int unet_tiff_compact_strips(const unsigned char* scratch, long long slot_bytes, const uint32_t* sizes, const long long* offsets, int count,
+                             unsigned char* out, long long out_bytes, void* stream);
 
 #ifdef __cplusplus
 }

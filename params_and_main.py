@@ -81,11 +81,14 @@ BLEND = "mean"
 # unet_amd.postprocess.PostProcess arguments, e.g. {"majority": 5, "sieve": 64} = a 5 x 5 majority filter, then a sieve that merges
 # regions under 64 px into their largest neighbour ("connectivity": 4 | 8; with class_zero set "frozen_class": 0 to keep NO_Data as it is)
 POSTPROCESS = None
+# compression of the prediction outputs: None (uncompressed, one strip) | "lzw" (LZW strips; the merged raster is encoded on the GPU and
+# only the compressed bytes reach the host) | ("lzw", 2) to add horizontal differencing (Predictor 2, class / integer outputs only)
+COMPRESS = None
 
 
 def main():
     global large_file, specific_class, all_classes, transforms, VALID_SCENES, self_attention, monitor, loss_func, LR_FINDER
-    global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND, POSTPROCESS
+    global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND, POSTPROCESS, COMPRESS
     t0 = time.time()
     if enable_extra_parameters:          # params_and_main.py:129-145
         import warnings
@@ -95,7 +98,7 @@ def main():
         ENCODER_FACTOR, LR_FINDER, VALID_SCENES, loss_func, monitor = 10, None, ["vali"], None, None
         all_classes, specific_class, enable_regression, large_file, max_empty = False, None, False, False, 0.9
         ARCHITECTURE, self_attention = xresnet34, False
-        TTA, BLEND, POSTPROCESS = None, "mean", None
+        TTA, BLEND, POSTPROCESS, COMPRESS = None, "mean", None, None
     if Create_tiles:
         from create_tiles_unet import split_raster
         split_raster(path_to_raster=image_path, path_to_mask=mask_path, base_dir=base_dir, patch_size=patch_size,
@@ -110,6 +113,8 @@ def main():
         extra = {} if BLEND == "mean" else {"blend": BLEND}
         if POSTPROCESS is not None:
             extra["postprocess"] = POSTPROCESS
+        if COMPRESS is not None:
+            extra["compress"], extra["predictor"] = COMPRESS if isinstance(COMPRESS, tuple) else (COMPRESS, 1)
         save_predictions(predict_model, predict_path, regression, merge, all_classes, specific_class, large_file, AOI, year,
                          validation_vision, class_zero, tta=TTA, **extra)
     print(f"Operation completed in {(time.time() - t0) / 60:.2f} minutes.")

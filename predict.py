@@ -34,6 +34,10 @@ And ``postprocess=`` (None | ``unet_amd.postprocess.PostProcess`` | a dict of it
 of the merged class mask on the device (``unet_amd/postprocess.py``), on rank 0, on the assembled mask -- after the rows of the other ranks
 have arrived and before ``store_tif`` -- so N ranks equal 1 rank by construction.  With one rank the mask goes from the argmax to the filters
 without leaving the device.  Only for the class mask of a merged prediction (ValueError otherwise, before the model is loaded).
+
+And ``compress=`` (None | "lzw") with ``predictor=`` (1 | 2): LZW-compressed GeoTIFF outputs.  A merged prediction is encoded where the merge
+assembled it -- on the device with one rank or RCCL (``unet_amd/tiffenc.py``), so only the compressed bytes reach the host -- and by the host
+encoder of ``unet_amd/tiffio.py`` otherwise (the int8 ``large_file`` merge, gloo ranks, per-tile outputs); the file is the same either way.
 """
 from __future__ import annotations
 
@@ -54,16 +58,30 @@ from unet_amd.feed import BatchFeeder, default_workers, torch_samples
 from unet_amd.learner import load_learner, open_tile
 from unet_amd.postprocess import check_postprocess
 from unet_amd.mosaic import MergePlan, blend_profile, check_blend, keep_windows, merge_order, sliding_windows
-from unet_amd.tiffio import read_tiff, tiff_info, write_tiff
+from unet_amd.tiffio import check_compress, read_tiff, tiff_info, write_tiff
 from unet_amd.tta import parse as tta_codes
 
 
-def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_zero=False):
-    """predict.py:19-52: GeoTIFF writer; class_zero shifts class ids back by one (0 was reserved for nodata)."""
-    a = np.asarray(data)
-    if class_zero and a.dtype.kind in "ui":
-        a = a - 1 if a.dtype.kind == "i" else (a.astype(np.int16) - 1)
-    write_tiff(output_file, a, geotransform=geotrans, tags=tags, nodata=nodata)
+def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_zero=False, compress=None, predictor=1,
+              timing: Optional[dict] = None):
+    """predict.py:19-52: GeoTIFF writer; class_zero shifts class ids back by one (0 was reserved for nodata).
+    compress="lzw" (predictor=2: horizontal differencing, integer samples): LZW strips -- a device tensor is shifted and encoded on the
+    device (unet_amd/tiffenc.py), a host array by the host encoder (tiffio.write_tiff); the two write the same file.  timing gains
+    write_seconds and file_bytes."""
+    t0 = time.perf_counter()
+    if isinstance(data, torch.Tensor) and data.is_cuda and compress is not None:
+        from unet_amd.tiffenc import write_tiff_device
+        t = data
+        if class_zero and not t.dtype.is_floating_point and t.dtype != torch.bool:
+            t = t - 1 if t.dtype.is_signed else (t.to(torch.int16) - 1)          # the dtypes of the host path below
+        write_tiff_device(output_file, t, geotransform=geotrans, tags=tags, nodata=nodata, compress=compress, predictor=predictor)
+    else:
+        a = data.cpu().numpy() if isinstance(data, torch.Tensor) else np.asarray(data)
+        if class_zero and a.dtype.kind in "ui":
+            a = a - 1 if a.dtype.kind == "i" else (a.astype(np.int16) - 1)
+        write_tiff(output_file, a, geotransform=geotrans, tags=tags, nodata=nodata, compress=compress, predictor=predictor)
+    if timing is not None:
+        timing.update(write_seconds=time.perf_counter() - t0, file_bytes=os.path.getsize(output_file))
 
 
 def _geo(path):
@@ -207,9 +225,11 @@ class _Merge:
             else:
                 ops.mosaic_accumulate_weighted(slab, self._profile(h), self._profile(w), self.mosaic, self.count, self.wsum, y0 - self.lo, x0)
 
-    def finish(self, want, postprocess=None, timing: Optional[dict] = None):
+    def finish(self, want, postprocess=None, timing: Optional[dict] = None, keep: bool = False):
         """want: "argmax" | "all" | int class index.  Returns (on rank 0) the full-size numpy array, None elsewhere.  postprocess: a
-        PostProcess applied to the assembled class mask on rank 0 (want == "argmax" only: check_postprocess)"""
+        PostProcess applied to the assembled class mask on rank 0 (want == "argmax" only: check_postprocess).  keep: the result stays
+        where it was assembled and comes back as a tensor -- on the device with one rank or RCCL, on the host for the int8 merge and
+        gloo -- for store_tif to encode it there"""
         rows, MW, MH = self.hi - self.lo, self.plan.MW, self.plan.MH
         if self.int8:
             merged, counter = self.mosaic[:, :rows].cpu().numpy(), self.count[:, :rows].cpu().numpy()
@@ -224,24 +244,26 @@ class _Merge:
             elif rows > 0:
                 ops.mosaic_finalize_rows_weighted(self.mosaic, self.count, self.wsum, 0, rows, am, fill=-9999.0 if self.raw else None)
             part = am[:rows] if want == "argmax" else (self.mosaic[:, :rows] if want == "all" else self.mosaic[want, :rows])
+        gather = (lambda p, planes: self._gather_rows(p, planes, True)) if keep else self._gather_rows
         if postprocess is None:
-            return self._gather_rows(part, want == "all")
+            return gather(part, want == "all")
         # one rank: the mask goes from the argmax to the filters on the device; N ranks: rank 0 uploads the assembled mask again
         full = part if self.world == 1 else self._gather_rows(part, False)
         if full is None:
             return None
         t0 = time.perf_counter()
         out, info = postprocess.run(torch.as_tensor(full).to(self.dev))
-        out = out.cpu().numpy()
+        if not keep:
+            out = out.cpu().numpy()
         if timing is not None:
             timing.update(postprocess_seconds=time.perf_counter() - t0, postprocess=info)
         return out
 
-    def _gather_rows(self, part: torch.Tensor, planes: bool):
-        """row strips of the ranks -> one array on rank 0 (only the requested band(s) travel)"""
+    def _gather_rows(self, part: torch.Tensor, planes: bool, keep: bool = False):
+        """row strips of the ranks -> one array on rank 0 (only the requested band(s) travel); keep: the tensor it was assembled in"""
         MW, MH = self.plan.MW, self.plan.MH
         if self.world == 1:
-            return part.cpu().numpy()
+            return part if keep else part.cpu().numpy()
         dist = _dist()
         host = dist.get_backend() == "gloo"
         part = (part.cpu() if host else part.to(self.dev)).contiguous()
@@ -260,15 +282,15 @@ class _Merge:
             buf = torch.empty(((self.C,) if planes else ()) + (hi - lo, MW), dtype=part.dtype, device=full.device)
             dist.recv(buf, r)
             full[sl + (slice(lo, hi),)] = buf
-        return full.cpu().numpy()
+        return full if keep else full.cpu().numpy()
 
 
 def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch, make_input: Callable, want, timing: Optional[dict] = None,
-               tta: Optional[Tuple[int, ...]] = None, blend: str = "mean", postprocess=None):
+               tta: Optional[Tuple[int, ...]] = None, blend: str = "mean", postprocess=None, keep: bool = False):
     """make_input(first, n, n_pad) -> ops.WindowBatch of placements [first, first + n) padded to n_pad windows (so that every
     forward runs on ONE batch geometry and no second set of activation buffers is allocated).  tta: parsed codes -- every batch runs
     len(tta) forwards of that same geometry and the averaged probabilities take the place of the softmax in the merge.  blend: "mean" |
-    "gaussian" (unet_amd/mosaic.py).  postprocess: a checked PostProcess or None"""
+    "gaussian" (unet_amd/mosaic.py).  postprocess: a checked PostProcess or None.  keep: _Merge.finish"""
     mg = _Merge(model, places, MH, MW, regression, int8_merge, rank, world, blend)
     t0 = time.perf_counter()
     batches = mg.plan.batches(rank, batch)
@@ -285,7 +307,7 @@ def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch
     mg.exchange()
     if timing is not None and not int8_merge and mg.hi > mg.lo:      # coverage of this rank's strip (before the division consumes nothing of it)
         timing.update(hits_min=int(mg.count.min().item()), hits_max=int(mg.count.max().item()))
-    out = mg.finish(want, postprocess, timing)
+    out = mg.finish(want, postprocess, timing, keep)
     if timing is not None:
         torch.cuda.synchronize()
         timing.update(seconds=time.perf_counter() - t0, windows_this_rank=sum(n for _, n in batches), windows=len(mg.plan.places),
@@ -296,6 +318,11 @@ def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch
 def _dist_ctx():
     from unet_amd.distributed import init_from_env
     return init_from_env()
+
+
+def _float_output(regression, all_classes, specific_class, large_file) -> bool:
+    """whether the output holds float samples (which Predictor 2 does not take): known from the arguments, before the model is loaded"""
+    return bool(regression or ((all_classes or specific_class is not None) and not large_file))
 
 
 def _want(regression, all_classes, specific_class):
@@ -341,7 +368,8 @@ def _raster_plan(wins: np.ndarray, size: int, H: int, W: int, batch_size: int):
 def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_empty: float = 0.9, dtype: str = "int8", nodata=None,
                    regression: bool = False, all_classes: bool = False, specific_class: Optional[int] = None, large_file: bool = False,
                    batch_size: int = 16, out_path=None, class_zero: bool = False, timing: Optional[dict] = None,
-                   batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None):
+                   batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
+                   return_array: bool = True):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -365,11 +393,19 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     postprocess  None | PostProcess | dict of its arguments (unet_amd/postprocess.py): majority filter and / or small-region sieve of the
              merged class mask on the device, before it is returned / written; only for the class mask (not regression, all_classes,
              specific_class: ValueError); timing gains postprocess_seconds and postprocess (the sieve's info)
+    compress  None | "lzw": out_path is written with LZW strips (predictor=2: horizontal differencing, integer outputs only).  The merged
+             array is encoded on the device where it was assembled there (one rank, RCCL ranks) and only the compressed bytes reach the
+             host; the int8 large_file merge and gloo ranks, which assemble on the host, use the host encoder -- the same file either way.
+             timing gains write_seconds and file_bytes
+    return_array  False (needs out_path): nothing is returned, and with compress="lzw" the merged array never goes to the host
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
     check_blend(blend, large_file)
     post = check_postprocess(postprocess, regression, all_classes, specific_class)
+    check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
+    if not return_array and out_path is None:
+        raise ValueError("return_array=False needs out_path: the prediction would go nowhere")
     model = getattr(model, "model", model)
     codes = tta_codes(tta, [(size, size)])
     rank, _, world = _dist_ctx()
@@ -409,15 +445,18 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
         return ops.WindowBatch(src, gtab, first, n_pad, size, size)
 
     want = _want(regression, all_classes, specific_class)
+    keep_out = compress is not None and out_path is not None          # the encoder takes the array where the merge assembled it
     with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
         out = _run_merge(model, places, MH, MW, regression, bool(large_file and not regression), rank, world, batch_size, make_input, want, timing,
-                         codes, blend, post)
+                         codes, blend, post, keep_out)
     if rank == 0 and out_path is not None:
         ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
-        store_tif(out_path, out, ogt, tags, -9999 if regression else None, class_zero)
+        store_tif(out_path, out, ogt, tags, -9999 if regression else None, class_zero, compress, predictor, timing)
     if timing is not None:
         timing.update(kept_windows=len(wins), all_windows=int(len(keep)), mosaic=(MH, MW))
-    return out if rank == 0 else None
+    if rank != 0 or not return_array:
+        return None
+    return out.cpu().numpy() if isinstance(out, torch.Tensor) else out
 
 
 # ----------------------------------------------------------------------------------------------- tile files: decode ahead of the GPU
@@ -570,15 +609,18 @@ def _tile_windows(batch_size: int, device, div255_twice: bool) -> Callable:
 
 def save_predictions(predict_model, predict_path, regression, merge=False, all_classes=False, specific_class=None, large_file=False,
                      AOI=None, year=None, validation_vision=True, class_zero=False, batch_size=16, timing: Optional[dict] = None,
-                     batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None):
+                     batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1):
     """tta: None | "flips" | "d4" | a tuple of D4 codes (see predict_raster and unet_amd/tta.py), merged and per-tile outputs alike.
     blend: "mean" | "gaussian" (see predict_raster): how the windows of a merged prediction combine; only with merge=True (per-tile
     outputs have no overlap) and not with large_file (ValueError before the model is loaded).
     postprocess: None | PostProcess | dict of its arguments (see predict_raster): only with merge=True and for the class mask (ValueError
     before the model is loaded).
+    compress / predictor: None | "lzw", 1 | 2 (see predict_raster).  The merged raster is encoded where the merge assembled it (on the
+    device with one rank or RCCL); per-tile outputs (merge=False) use the host encoder.
     validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
     check_blend(blend, large_file, merge)
     post = check_postprocess(postprocess, regression, all_classes, specific_class, merge)
+    check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
     rank, local_rank, world = _dist_ctx()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model
@@ -596,10 +638,11 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     windows = _tile_windows(batch_size, model._device, learn.dls.train_ds.dtype == "int16")
     if merge:
         out, gt = _save_merged(model, tiles, geos, windows, rank, world, regression, _want(regression, all_classes, specific_class),
-                               bool(large_file and not regression), batch_size, batch_invariant, codes, blend, timing, post)
+                               bool(large_file and not regression), batch_size, batch_invariant, codes, blend, timing, post,
+                               compress is not None)
     else:
         _save_tiles(model, tiles, geos, windows, rank, world, output_folder, regression, all_classes, specific_class, large_file, class_zero,
-                    batch_size, batch_invariant, codes)
+                    batch_size, batch_invariant, codes, compress, predictor)
         if world > 1:
             _dist().barrier()
     if timing is not None:
@@ -611,13 +654,13 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     if rank != 0:
         return None
     name = "_".join(filter(None, [AOI, year, model_name, "prediction"])) + ".tif"
-    store_tif(output_folder / name, out, gt, geos[0][1], -9999 if regression else None, class_zero)
+    store_tif(output_folder / name, out, gt, geos[0][1], -9999 if regression else None, class_zero, compress, predictor, timing)
     print(f"Prediction stored in {output_folder}.")
     return output_folder if regression else output_folder / name
 
 
 def _save_merged(model, tiles, geos, windows: Callable, rank, world, regression, want, int8_merge, batch_size, batch_invariant, codes, blend,
-                 timing, postprocess=None):
+                 timing, postprocess=None, keep: bool = False):
     """overlap merge (predict.py:257-355) of this rank's share of the tiles -> (merged array on rank 0, None elsewhere; geotransform of
     the mosaic).  The extent follows from the tiles' geotransforms and sizes, which are known from the headers BEFORE any tile is
     predicted: every batch is accumulated into the device mosaic as soon as it is computed and its probabilities are dropped (the
@@ -651,12 +694,12 @@ def _save_merged(model, tiles, geos, windows: Callable, rank, world, regression,
 
         with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):          # (see predict_raster)
             out = _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch_size, make_input, want, timing, codes, blend,
-                             postprocess)
+                             postprocess, keep)
     return out, [ulx_full, xres, 0.0, uly_full, 0.0, yres]
 
 
 def _save_tiles(model, tiles, geos, windows: Callable, rank, world, output_folder, regression, all_classes, specific_class, large_file,
-                class_zero, batch_size, batch_invariant, codes):
+                class_zero, batch_size, batch_invariant, codes, compress=None, predictor=1):
     """one output file per tile (predict.py:224-254); tile i -> rank i mod world"""
     dev, C = model._device, model.n_out
     mine = list(range(rank, len(tiles), world))
@@ -697,4 +740,4 @@ def _save_tiles(model, tiles, geos, windows: Callable, rank, world, output_folde
                 if large_file and out.dtype.kind == "f" and out.max() <= 1 and (all_classes or specific_class):
                     out = np.around(out * LARGE_FILE_SCALE).astype(np.int8)
                 name = t.name if t.suffix != ".npy" else t.stem + ".tif"
-                store_tif(output_folder / name, out, gt, tags, None, class_zero)
+                store_tif(output_folder / name, out, gt, tags, None, class_zero, compress, predictor)

@@ -214,6 +214,10 @@ _sig = {
     "unet_mosaic_accumulate_windows": (i, [vp, i, i, i, i, i, vp, i, i, i, i, vp, vp, i, i, i, i, vp]),
     "unet_tiff_lzw_decode": (ll, [vp, ll, vp, ll]),
     "unet_tiff_packbits_decode": (ll, [vp, ll, vp, ll]),
+    "unet_tiff_lzw_cap": (ll, [ll]),
+    "unet_tiff_lzw_encode": (ll, [vp, ll, vp, ll]),
+    "unet_tiff_encode_strips": (i, [vp, i, i, i, i, ll, ll, i, i, ll, i, vp, ll, vp, vp]),
+    "unet_tiff_compact_strips": (i, [vp, ll, vp, vp, i, vp, ll, vp]),
     "unet_mosaic_finalize_rows": (i, [vp, vp, i, i, i, i, i, vp, c_float_p, vp]),
     "unet_tiles_stage": (i, [vp, i, i, i, i, i, i, C.c_ulonglong, C.c_ulonglong, vp, vp]),
     "unet_mask_stage": (i, [vp, i, i, i, i, C.c_ulonglong, C.c_ulonglong, vp, i, vp]),

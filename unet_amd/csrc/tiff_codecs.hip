@@ -58,6 +58,80 @@ extern "C" long long unet_tiff_lzw_decode(const unsigned char* src, long long n,
     return out;
 }
 
+// The encoder of the writer (unet_amd/tiffio.py write_tiff(compress="lzw")); csrc/tiff_encode.hip is the same rule on the device and
+// tests/tiff_lzw_ref.py the same rule in Python -- the three produce equal bytes.  Every strip: Clear at 9 bits, next = 258; greedy
+// longest match; a pair (prefix, byte) that is not in the table emits prefix, becomes code `next`, and then either next == 4094 emits
+// Clear (at 12 bits) and empties the table, or next > 2^width - 1 widens the codes (the early change); at the end the pending prefix, the
+// same step once more, EOI, zero padding.  An empty strip is Clear, EOI.  unet_tiff_lzw_cap(n) bytes always suffice: at most one 12-bit
+// code per byte, one Clear per 3836 additions, the Clear / EOI frame.
+// The dictionary is an open-addressed table of 8192 words, word = key << 12 | code with key = prefix << 8 | byte, all ones = empty.
+extern "C" long long unet_tiff_lzw_cap(long long n) { return n < 0 ? -1 : (3 * (n + n / 3836 + 4) + 1) / 2; }
+
+namespace {
+struct LzwBits {          // MSB-first packer into dst[0, cap)
+    unsigned char* dst;
+    long long cap, out;
+    uint64_t acc;
+    int nbits;
+    bool put(int code, int width) {
+        acc = (acc << width) | (uint64_t)code;
+        nbits += width;
+        while (nbits >= 8) {
+            if (out >= cap) return false;
+            dst[out++] = (unsigned char)(acc >> (nbits - 8));
+            nbits -= 8;
+        }
+        return true;
+    }
+    bool flush() {
+        if (nbits == 0) return true;
+        if (out >= cap) return false;
+        dst[out++] = (unsigned char)(acc << (8 - nbits));
+        nbits = 0;
+        return true;
+    }
+};
+}  // namespace
+
+extern "C" long long unet_tiff_lzw_encode(const unsigned char* src, long long n, unsigned char* dst, long long cap) {
+    if ((src == nullptr && n > 0) || dst == nullptr || n < 0 || cap < 0) return -1;
+    enum { CLEAR = 256, EOI = 257, LAST = 4094, SLOTS = 8192 };
+    uint32_t table[SLOTS];
+    memset(table, 0xFF, sizeof(table));
+    LzwBits b{dst, cap, 0, 0, 0};
+    int width = 9, next = 258;
+    // after a code has gone out: the table grows by one (at the end of the strip only the counter does); Clear or the early change
+    auto step = [&]() -> bool {
+        if (++next == LAST) {
+            if (!b.put(CLEAR, width)) return false;
+            memset(table, 0xFF, sizeof(table));
+            next = 258;
+            width = 9;
+        } else if (next > (1 << width) - 1) {
+            ++width;
+        }
+        return true;
+    };
+    if (!b.put(CLEAR, 9)) return -1;
+    if (n > 0) {
+        uint32_t prefix = src[0];
+        for (long long i = 1; i < n; ++i) {
+            const uint32_t key = (prefix << 8) | src[i];
+            uint32_t h = (key * 2654435761u) >> 19;
+            uint32_t e;
+            while ((e = table[h]) != 0xFFFFFFFFu && (e >> 12) != key) h = (h + 1) & (SLOTS - 1);
+            if (e != 0xFFFFFFFFu) { prefix = e & 0xFFFu; continue; }
+            if (!b.put((int)prefix, width)) return -1;
+            table[h] = (key << 12) | (uint32_t)next;
+            if (!step()) return -1;
+            prefix = src[i];
+        }
+        if (!b.put((int)prefix, width) || !step()) return -1;
+    }
+    if (!b.put(EOI, width) || !b.flush()) return -1;
+    return b.out;
+}
+
 // PackBits (TIFF 6.0 section 9): n in [0,127]: copy n + 1 literal bytes; n in [-127,-1]: repeat the next byte 1 - n times; -128: no-op
 extern "C" long long unet_tiff_packbits_decode(const unsigned char* src, long long n, unsigned char* dst, long long cap) {
     if (src == nullptr || dst == nullptr || n < 0 || cap < 0) return -1;

@@ -1446,6 +1446,61 @@ def postprocess_counters(counters: torch.Tensor):
     return int(host[0]), int(host[1])
 
 
+# ---------------------------------------------------------------------------------------------- GeoTIFF strips on the device (csrc/tiff_encode.hip)
+
+def tiff_lzw_cap(n: int) -> int:
+    """bytes that always hold the LZW stream of an n-byte strip"""
+    return int(lib.unet_tiff_lzw_cap(int(n)))
+
+
+def tiff_slot_bytes(strip_bytes: int) -> int:
+    """the slot of one strip in the scratch of tiff_encode_strips: its capacity rounded up to 16 bytes"""
+    return -(-tiff_lzw_cap(strip_bytes) // 16) * 16
+
+
+def tiff_encode_strips(img: torch.Tensor, rows_per_strip: int, predictor: int, first: int, count: int, scratch: torch.Tensor,
+                       sizes: torch.Tensor):
+    """LZW-encodes strips [first, first + count) of img [P, H, W] (1-, 2- or 4-byte samples; any row / plane stride, unit column stride)
+    into scratch (uint8, count slots of tiff_slot_bytes) and their byte counts into sizes (int32 [count], read as unsigned)"""
+    what = "tiff_encode_strips"
+    if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dim() != 3 or img.element_size() not in (1, 2, 4) or img.is_complex():
+        raise ValueError(f"{what}: img must be a [P, H, W] GPU tensor of 1-, 2- or 4-byte samples")
+    P, H, W = (int(v) for v in img.shape)
+    if min(P, H, W) < 1 or img.stride(2) != 1 or img.stride(1) < W or (P > 1 and img.stride(0) < 1):
+        raise ValueError(f"{what}: img {tuple(img.shape)} with strides {img.stride()} needs contiguous rows and positive strides")
+    es = img.element_size()
+    if isinstance(rows_per_strip, bool) or not isinstance(rows_per_strip, int) or not 1 <= rows_per_strip <= H or rows_per_strip * W * es > 2 ** 31 - 1:
+        raise ValueError(f"{what}: rows_per_strip must be an int in 1..{H} with a strip below 2^31 bytes, got {rows_per_strip!r}")
+    if predictor not in (1, 2) or (predictor == 2 and img.dtype.is_floating_point):
+        raise ValueError(f"{what}: predictor must be 1, or 2 on integer samples (got {predictor!r} on {img.dtype})")
+    total = P * -(-H // rows_per_strip)
+    if not (0 <= first and 1 <= count and first + count <= total):
+        raise ValueError(f"{what}: strips [{first}, {first + count}) of {total}")
+    slot = tiff_slot_bytes(rows_per_strip * W * es)
+    _pp_tensor(what, "scratch", scratch, torch.uint8)
+    _pp_tensor(what, "sizes", sizes, torch.int32)
+    if scratch.numel() < count * slot or sizes.numel() < count or scratch.device != img.device or sizes.device != img.device:
+        raise ValueError(f"{what}: needs {count * slot} scratch bytes and {count} sizes on the image's device")
+    check(lib.unet_tiff_encode_strips(img.data_ptr(), es, P, H, W, img.stride(1), img.stride(0) if P > 1 else H * img.stride(1), rows_per_strip,
+                                      predictor, first, count, scratch.data_ptr(), slot, sizes.data_ptr(), _stream()), what)
+    return slot
+
+
+def tiff_compact_strips(scratch: torch.Tensor, slot: int, sizes: torch.Tensor, offsets: torch.Tensor, count: int, out: torch.Tensor):
+    """out[offsets[j] : offsets[j] + sizes[j]] = slot j of scratch; offsets int64 [count] = exclusive prefix sum of sizes"""
+    what = "tiff_compact_strips"
+    _pp_tensor(what, "scratch", scratch, torch.uint8)
+    _pp_tensor(what, "sizes", sizes, torch.int32)
+    _pp_tensor(what, "offsets", offsets, torch.int64)
+    _pp_tensor(what, "out", out, torch.uint8)
+    if count < 1 or slot < 4 or scratch.numel() < count * slot or sizes.numel() < count or offsets.numel() < count:
+        raise ValueError(f"{what}: {count} slots of {slot} bytes do not fit the buffers")
+    if any(t.device != scratch.device for t in (sizes, offsets, out)):
+        raise ValueError(f"{what}: all buffers must live on one device")
+    check(lib.unet_tiff_compact_strips(scratch.data_ptr(), slot, sizes.data_ptr(), offsets.data_ptr(), count, out.data_ptr(), out.numel(),
+                                       _stream()), what)
+
+
 # ---------------------------------------------------------------------------------------------- border distance and weight map (csrc/edt.hip)
 
 EDT_MAX_SIDE = 8192          # 2 * 8191^2 < 2^31: the squared distance fits int32

@@ -10,7 +10,8 @@ JPEG-in-TIFF (Compression 7 with the JPEGTables tag: baseline 8-bit, what GDAL's
 as RGB, as it does from GDAL) is decoded to the bytes libtiff + libjpeg produce (csrc/host/tiff_jpeg.cpp).  Anything else (old-style JPEG 6,
 12-bit / progressive JPEG, CCITT, ...) raises loudly.
 The byte-oriented decoders are C functions (csrc/tiff_codecs.hip: in libunet_hip.so, and linked by g++ alone -- together with the JPEG
-decoder -- into the host-only libunet_tiff.so); files are memory-mapped for reading and written uncompressed.
+decoder -- into the host-only libunet_tiff.so); files are memory-mapped for reading and written uncompressed, or with compress="lzw" as
+LZW strips (unet_tiff_lzw_encode in the same file; StripWriter is the layout, shared with the device encoder of unet_amd/tiffenc.py).
 """
 from __future__ import annotations
 
@@ -75,9 +76,9 @@ _codec_lib = None
 
 
 def _codecs():
-    """the two byte-oriented TIFF decoders (csrc/tiff_codecs.hip: plain C++, no device code).  ``python -m unet_amd.build`` also links them
+    """the two byte-oriented TIFF decoders and the LZW encoder (csrc/tiff_codecs.hip: plain C++, no device code).  ``python -m unet_amd.build`` also links them
     into a host-only ``libunet_tiff.so`` (g++), so a tile-preparation box without the HIP runtime reads the rasters GDAL writes by default;
-    libunet_hip.so exports the same two symbols."""
+    libunet_hip.so exports the same symbols."""
     global _codec_lib
     if _codec_lib is None:
         import ctypes as C
@@ -86,7 +87,7 @@ def _codecs():
             lib = C.CDLL(str(host))
         else:
             from ._lib import lib
-        for fn in (lib.unet_tiff_lzw_decode, lib.unet_tiff_packbits_decode):
+        for fn in (lib.unet_tiff_lzw_decode, lib.unet_tiff_packbits_decode, lib.unet_tiff_lzw_encode):
             fn.restype, fn.argtypes = C.c_longlong, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong]
         try:                       # include/unet_tiff.h: the JPEG decoder lives in the host-only library alone
             lib.unet_tiff_jpeg_decode.restype = C.c_longlong
@@ -96,6 +97,16 @@ def _codecs():
             lib.has_jpeg = False
         _codec_lib = lib
     return _codec_lib
+
+
+def _threads() -> int:
+    """threads of the strip decode / encode pools: from the CPU affinity (2..8), UNET_TIFF_THREADS overrides"""
+    import os
+    try:
+        nthr = max(2, min(8, len(os.sched_getaffinity(0))))
+    except (AttributeError, OSError):
+        nthr = 4
+    return int(os.environ.get("UNET_TIFF_THREADS", nthr))
 
 
 def _decoder(comp: int, path):
@@ -327,11 +338,7 @@ def read_tiff(path) -> Tuple[np.ndarray, Dict]:
             out[p, r0:r0 + h, c0:c0 + w] = t[:h, :w]
 
     total = planes * H * W * pix * dt.itemsize
-    try:
-        nthr = max(2, min(8, len(os.sched_getaffinity(0))))
-    except (AttributeError, OSError):
-        nthr = 4
-    nthr = int(os.environ.get("UNET_TIFF_THREADS", nthr))
+    nthr = _threads()
     if comp != 1 and len(jobs) >= 16 and total >= (32 << 20) and nthr > 1:
         from concurrent.futures import ThreadPoolExecutor
         step = max(1, -(-len(jobs) // (nthr * 8)))
@@ -342,10 +349,207 @@ def read_tiff(path) -> Tuple[np.ndarray, Dict]:
     return finish(out)
 
 
-def write_tiff(path, arr: np.ndarray, geotransform=None, tags: Optional[Dict[int, tuple]] = None, nodata=None, bigtiff: Optional[bool] = None) -> None:
+def lzw_cap(n: int) -> int:
+    """bytes that always hold the LZW stream of an n-byte strip: at most one 12-bit code per byte, one Clear per 3836 table additions,
+    the Clear / EOI frame"""
+    return (3 * (n + n // 3836 + 4) + 1) // 2
+
+
+def check_compress(compress, predictor=1, floats: bool = False):
+    """the compress= / predictor= arguments of the writers, validated from the arguments alone -> (compress, predictor)"""
+    if compress not in (None, "lzw"):
+        raise ValueError(f"compress must be None or 'lzw', got {compress!r}")
+    if isinstance(predictor, bool) or predictor not in (1, 2):
+        raise ValueError(f"predictor must be 1 or 2 (horizontal differencing), got {predictor!r}")
+    if predictor == 2 and compress is None:
+        raise ValueError("predictor=2 needs compress='lzw': an uncompressed file is not differenced")
+    if predictor == 2 and floats:
+        raise ValueError("predictor=2 is horizontal differencing of integer samples; floating-point differencing (Predictor 3) is not written")
+    return compress, int(predictor)
+
+
+def _samples(arr) -> np.ndarray:
+    """[C, H, W] samples of a type the writers store (bool -> uint8, int64 -> int32, float64 -> float32)"""
+    a = np.asarray(arr)
+    if a.ndim == 2:
+        a = a[None]
+    for src, dst in ((np.bool_, np.uint8), (np.int64, np.int32), (np.float64, np.float32)):
+        if a.dtype == src:
+            a = a.astype(dst)
+    return a
+
+
+class StripWriter:
+    """The file layout of compress="lzw", filled strip by strip by whoever encodes (write_tiff below: the host encoder; unet_amd/tiffenc.py:
+    the device).  Little-endian; LZW strips of rows_per_strip rows (default: the largest row count whose strip is at most 64 KiB, at
+    least one row); PlanarConfiguration 2 for C > 1 -- strip p * strips_per_plane + s is strip s of band p, GDAL's INTERLEAVE=BAND;
+    Predictor tag 317 when predictor == 2.  The strip byte counts are known only after encoding, so the IFD is placed AFTER the data:
+    header, strips in order, IFD with its StripOffsets / StripByteCounts arrays, and close() patches the header's IFD offset.  BigTIFF
+    is chosen from the worst-case byte count (every strip at its capacity), so the choice does not depend on the content.
+    The georeferencing tags, GDAL_NODATA, SampleFormat and ExtraSamples are those of the uncompressed writer."""
+
+    def __init__(self, path, C: int, H: int, W: int, dtype, rows_per_strip=None, predictor: int = 1, geotransform=None,
+                 tags: Optional[Dict[int, tuple]] = None, nodata=None, bigtiff: Optional[bool] = None):
+        self.dtype = np.dtype(dtype)
+        if self.dtype.kind not in "uif" or self.dtype.itemsize not in (1, 2, 4) or (self.dtype.kind == "f" and self.dtype.itemsize != 4):
+            raise ValueError(f"compress='lzw': {self.dtype} samples are not written (8 / 16 / 32-bit integers and float32 are)")
+        check_compress("lzw", predictor, self.dtype.kind == "f")
+        if min(C, H, W) < 1:
+            raise ValueError(f"compress='lzw': empty image {C} x {H} x {W}")
+        es = self.dtype.itemsize
+        if rows_per_strip is None:
+            rows_per_strip = max(1, (64 << 10) // (W * es))
+        if isinstance(rows_per_strip, bool) or not isinstance(rows_per_strip, (int, np.integer)) or rows_per_strip < 1:
+            raise ValueError(f"rows_per_strip must be None or an int >= 1, got {rows_per_strip!r}")
+        self.C, self.H, self.W, self.predictor = C, H, W, predictor
+        self.rows_per_strip = rps = min(int(rows_per_strip), H)
+        self.strips_per_plane = spp = -(-H // rps)
+        self.strips = [(p, s * rps, min(rps, H - s * rps)) for p in range(C) for s in range(spp)]          # (band, first row, rows) in file order
+        worst = sum(lzw_cap(rows * W * es) for _, _, rows in self.strips[:spp]) * C
+        self.big = (worst > (1 << 32) - (1 << 20)) if bigtiff is None else bool(bigtiff)
+        self.geo = dict(tags or {})
+        if geotransform is not None:
+            ulx, xres, _, uly, _, yres = geotransform
+            self.geo[33550] = (abs(xres), abs(yres), 0.0)
+            self.geo[33922] = (0.0, 0.0, 0.0, ulx, uly, 0.0)
+        if nodata is not None:
+            self.geo[42113] = (str(nodata),)
+        self.offsets, self.counts = [], []
+        self.f = open(path, "wb")
+        self.f.write(b"II" + (struct.pack("<HHHQ", 43, 8, 0, 0) if self.big else struct.pack("<HI", 42, 0)))
+        self.pos = 16 if self.big else 8
+
+    def append(self, data, sizes) -> None:
+        """the next len(sizes) strips: `data` (bytes-like) holds their streams back to back"""
+        sizes = [int(s) for s in sizes]
+        if len(self.counts) + len(sizes) > len(self.strips) or sum(sizes) != len(data):
+            raise ValueError(f"StripWriter.append: {len(sizes)} strips of {sum(sizes)} bytes do not match the data ({len(data)} bytes) or the layout")
+        for s in sizes:
+            self.offsets.append(self.pos)
+            self.counts.append(s)
+            self.pos += s
+        self.f.write(data)
+
+    def close(self) -> int:
+        """writes the IFD behind the data and closes the file -> the file's size in bytes"""
+        if len(self.counts) != len(self.strips):
+            self.f.close()
+            raise ValueError(f"StripWriter.close: {len(self.counts)} of {len(self.strips)} strips were written")
+        big, C = self.big, self.C
+        if not big and self.pos > (1 << 32) - (1 << 20):
+            self.f.close()
+            raise ValueError("the compressed data does not fit a classic TIFF's 32-bit offsets: pass bigtiff=None or True")
+        off_t, off_fmt, inl = (16, "Q", 8) if big else (4, "I", 4)
+        kind = {"u": 1, "i": 2, "f": 3}[self.dtype.kind]
+        entries = []          # (tag, type, count, payload-bytes)
+
+        def add(tag, typ, vals):
+            if typ == 2:
+                payload = vals.encode("latin1") + b"\0"
+                cnt = len(payload)
+            else:
+                payload = struct.pack("<" + _TYPES[typ][0][0] * len(vals), *vals)
+                cnt = len(vals)
+            entries.append((tag, typ, cnt, payload))
+
+        add(256, 4, [self.W]); add(257, 4, [self.H]); add(258, 3, [self.dtype.itemsize * 8] * C); add(259, 3, [5])
+        add(262, 3, [1]); add(273, off_t, self.offsets); add(277, 3, [C]); add(278, 4, [self.rows_per_strip]); add(279, off_t, self.counts)
+        add(284, 3, [2 if C > 1 else 1])
+        if self.predictor == 2:
+            add(317, 3, [2])
+        if C > 1:
+            add(338, 3, [0] * (C - 1))
+        add(339, 3, [kind] * C)
+        for t in sorted(self.geo):
+            v = self.geo[t]
+            if t in (34737, 42113):
+                add(t, 2, v[0] if isinstance(v, tuple) else v)
+            elif t == 34735:
+                add(t, 3, list(v))
+            else:
+                add(t, 12, list(v))
+        entries.sort(key=lambda e: e[0])
+        pad = self.pos % 2                                          # an IFD starts on a word boundary
+        ifd_off = self.pos + pad
+        n = len(entries)
+        extra_off = ifd_off + (8 + 20 * n + 8 if big else 2 + 12 * n + 4)
+        extra, body = b"", b""
+        for tag, typ, cnt, payload in entries:
+            if len(payload) <= inl:
+                val = payload.ljust(inl, b"\0")
+            else:
+                if len(extra) % 2:
+                    extra += b"\0"
+                val = struct.pack("<" + off_fmt, extra_off + len(extra))
+                extra += payload
+            body += struct.pack("<HH" + off_fmt, tag, typ, cnt) + val
+        self.f.write(b"\0" * pad + struct.pack("<Q" if big else "<H", n) + body + struct.pack("<" + off_fmt, 0) + extra)
+        size = self.f.tell()
+        self.f.seek(8 if big else 4)
+        self.f.write(struct.pack("<" + off_fmt, ifd_off))
+        self.f.close()
+        return size
+
+
+def _predicted_le(block: np.ndarray, predictor: int) -> np.ndarray:
+    """[rows, W] samples -> the strip's bytes: differences per sample along the row modulo 2^bits (Predictor 2), then little-endian"""
+    if predictor == 2:
+        d = block.copy()
+        d[:, 1:] -= block[:, :-1]          # (integer arrays wrap)
+        block = d
+    return np.ascontiguousarray(block.astype(block.dtype.newbyteorder("<"), copy=False)).view(np.uint8).reshape(-1)
+
+
+def _write_lzw(path, a: np.ndarray, geotransform, tags, nodata, bigtiff, predictor, rows_per_strip) -> int:
+    """write_tiff(compress="lzw") of host samples: the strips are encoded by unet_tiff_lzw_encode on a thread pool (ctypes releases the
+    GIL), a batch of strips at a time, and appended in order -- the file does not depend on the thread count"""
+    lib = _codecs()
+    C, H, W = a.shape
+    w = StripWriter(path, C, H, W, a.dtype, rows_per_strip, predictor, geotransform, tags, nodata, bigtiff)
+
+    def encode(strip):
+        p, r0, rows = strip
+        src = _predicted_le(a[p, r0:r0 + rows], predictor)
+        cap = lzw_cap(src.size)
+        dst = np.empty(cap, dtype=np.uint8)
+        got = lib.unet_tiff_lzw_encode(src.ctypes.data, src.size, dst.ctypes.data, cap)
+        if got < 0:
+            raise RuntimeError(f"{path}: the LZW encoder overran its capacity of {cap} bytes for a strip of {src.size}")
+        return dst[:got]
+
+    try:
+        nthr = _threads()
+        if nthr > 1 and len(w.strips) >= 16 and a.nbytes >= (4 << 20):
+            from concurrent.futures import ThreadPoolExecutor
+            step = nthr * 16
+            with ThreadPoolExecutor(max_workers=nthr) as ex:
+                for i in range(0, len(w.strips), step):
+                    enc = list(ex.map(encode, w.strips[i:i + step]))
+                    w.append(b"".join(e.data for e in enc), [e.size for e in enc])
+        else:
+            for strip in w.strips:
+                e = encode(strip)
+                w.append(e.data, [e.size])
+    except BaseException:
+        w.f.close()
+        raise
+    return w.close()
+
+
+def write_tiff(path, arr: np.ndarray, geotransform=None, tags: Optional[Dict[int, tuple]] = None, nodata=None, bigtiff: Optional[bool] = None,
+               compress=None, predictor: int = 1, rows_per_strip=None) -> None:
     """Uncompressed, single strip, pixel-interleaved little-endian TIFF of a [C,H,W] or [H,W] array.  bigtiff None: BigTIFF (64-bit offsets)
     when the file would not fit 32-bit offsets -- what GDAL's BIGTIFF=IF_NEEDED does for the reference's outputs (predict.py:19-52): the
-    all-classes probabilities of a 20000 x 20000 scene are 8 GB."""
+    all-classes probabilities of a 20000 x 20000 scene are 8 GB.
+    compress="lzw": LZW strips in the layout of StripWriter (band-sequential, IFD behind the data), encoded on the host; predictor=2 adds
+    horizontal differencing (integer samples only); rows_per_strip None: strips of at most 64 KiB."""
+    if compress is not None or predictor != 1 or rows_per_strip is not None:
+        a = _samples(arr)
+        check_compress(compress, predictor, a.dtype.kind == "f")
+        if compress is None:
+            raise ValueError("rows_per_strip needs compress='lzw': the uncompressed file is one strip")
+        _write_lzw(path, a, geotransform, tags, nodata, bigtiff, predictor, rows_per_strip)
+        return
     a = np.asarray(arr)
     if a.ndim == 2:
         a = a[None]
