@@ -717,6 +717,34 @@ int unet_tiff_encode_strips(const void* src, int elem_size, int P, int H, int W,
 int unet_tiff_compact_strips(const unsigned char* scratch, long long slot_bytes, const uint32_t* sizes, const long long* offsets, int count,
                              unsigned char* out, long long out_bytes, void* stream);
 
+/* -------------------------------------------- tiled GeoTIFFs with overviews on the device --
+ * DESIGN 3.17.  unet_tiff_encode_tiles (csrc/tiff_encode.hip): the encoder of unet_tiff_encode_strips over square tiles of `tile` samples a
+ *   side (a multiple of 16 in 16..1024).  Tile k = (p * tiles_down + j) * tiles_across + i, the TIFF order; tiles [first, first + count) ->
+ *   scratch + j * slot_bytes, sizes[j].  Samples beyond the right / bottom edge of the image are zero; predictor 2 runs along the whole
+ *   padded tile row.  slot_bytes: a multiple of 4, at least unet_tiff_lzw_cap(tile * tile * elem_size).  unet_tiff_compact_strips packs
+ *   the slots as it packs strips.  unet_tiff_encode_tile_levels: one launch over the tiles of up to UNET_TIFF_MAX_LEVELS images of the same
+ *   sample type and plane count, one image after the other in the order given (a writer passes the pyramid smallest level first), so
+ *   that the small levels of a pyramid do not cost a launch -- one tile's latency -- each; unet_tiff_encode_tiles is its one-image form.
+ * unet_tiff_reduce_level (csrc/tiff_pyramid.hip): the next overview level of [P, H, W] samples (strides in samples, W contiguous samples per
+ *   row) -> dst, dense [P, ceil(H / 2), ceil(W / 2)].  kind: 0 unsigned, 1 signed, 2 float (4 bytes); resampling: 0 nearest, 1 mode
+ *   (integers only), 2 average; the rule per clipped 2 x 2 block is stated at the top of csrc/tiff_pyramid.hip.  has_nodata / nodata: samples
+ *   equal to nodata (NaN: NaN samples) do not count, a block without a valid sample gives nodata; an integer nodata must be a sample of the
+ *   type.  H x W must be larger than 1 x 1.  Deterministic, no atomics.
+ * Bad arguments return -1 before any launch. */
+#define UNET_TIFF_MAX_LEVELS 32
+typedef struct unet_tiff_level {
+    const void* src;
+    long long row_stride, plane_stride; /* in samples */
+    int H, W;
+} unet_tiff_level;
+int unet_tiff_encode_tiles(const void* src, int elem_size, int P, int H, int W, long long row_stride, long long plane_stride, int tile,
+                           int predictor, long long first, int count, unsigned char* scratch, long long slot_bytes, uint32_t* sizes,
+                           void* stream);
+int unet_tiff_encode_tile_levels(const unet_tiff_level* levels, int nlevels, int elem_size, int P, int tile, int predictor, long long first,
+                                 int count, unsigned char* scratch, long long slot_bytes, uint32_t* sizes, void* stream);
+int unet_tiff_reduce_level(const void* src, int elem_size, int kind, int P, int H, int W, long long row_stride, long long plane_stride,
+                           int resampling, int has_nodata, double nodata, void* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

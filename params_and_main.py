@@ -84,11 +84,16 @@ POSTPROCESS = None
 # compression of the prediction outputs: None (uncompressed, one strip) | "lzw" (LZW strips; the merged raster is encoded on the GPU and
 # only the compressed bytes reach the host) | ("lzw", 2) to add horizontal differencing (Predictor 2, class / integer outputs only)
 COMPRESS = None
+# layout of the merged prediction raster (needs COMPRESS): TILE None (strips) | a multiple of 16 in 16..1024, 256 being the usual choice
+# (square LZW tiles); OVERVIEWS None | "auto" | "mode" | "average" | "nearest" (needs TILE): the overview pyramid behind the full-resolution
+# image, i.e. a cloud-optimised GeoTIFF -- "auto" takes "mode" for class masks and "average" for everything else
+TILE = None
+OVERVIEWS = None
 
 
 def main():
     global large_file, specific_class, all_classes, transforms, VALID_SCENES, self_attention, monitor, loss_func, LR_FINDER
-    global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND, POSTPROCESS, COMPRESS
+    global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS
     t0 = time.time()
     if enable_extra_parameters:          # params_and_main.py:129-145
         import warnings
@@ -98,7 +103,7 @@ def main():
         ENCODER_FACTOR, LR_FINDER, VALID_SCENES, loss_func, monitor = 10, None, ["vali"], None, None
         all_classes, specific_class, enable_regression, large_file, max_empty = False, None, False, False, 0.9
         ARCHITECTURE, self_attention = xresnet34, False
-        TTA, BLEND, POSTPROCESS, COMPRESS = None, "mean", None, None
+        TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS = None, "mean", None, None, None, None
     if Create_tiles:
         from create_tiles_unet import split_raster
         split_raster(path_to_raster=image_path, path_to_mask=mask_path, base_dir=base_dir, patch_size=patch_size,
@@ -115,6 +120,10 @@ def main():
             extra["postprocess"] = POSTPROCESS
         if COMPRESS is not None:
             extra["compress"], extra["predictor"] = COMPRESS if isinstance(COMPRESS, tuple) else (COMPRESS, 1)
+        if TILE is not None:
+            extra["tile"] = TILE
+        if OVERVIEWS is not None:
+            extra["overviews"] = OVERVIEWS
         save_predictions(predict_model, predict_path, regression, merge, all_classes, specific_class, large_file, AOI, year,
                          validation_vision, class_zero, tta=TTA, **extra)
     print(f"Operation completed in {(time.time() - t0) / 60:.2f} minutes.")

@@ -58,28 +58,31 @@ from unet_amd.feed import BatchFeeder, default_workers, torch_samples
 from unet_amd.learner import load_learner, open_tile
 from unet_amd.postprocess import check_postprocess
 from unet_amd.mosaic import MergePlan, blend_profile, check_blend, keep_windows, merge_order, sliding_windows
-from unet_amd.tiffio import check_compress, read_tiff, tiff_info, write_tiff
+from unet_amd.tiffio import check_compress, check_tiling, read_tiff, resolve_overviews, tiff_info, write_tiff
 from unet_amd.tta import parse as tta_codes
 
 
 def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_zero=False, compress=None, predictor=1,
-              timing: Optional[dict] = None):
+              timing: Optional[dict] = None, tile=None, overviews=None):
     """predict.py:19-52: GeoTIFF writer; class_zero shifts class ids back by one (0 was reserved for nodata).
     compress="lzw" (predictor=2: horizontal differencing, integer samples): LZW strips -- a device tensor is shifted and encoded on the
     device (unet_amd/tiffenc.py), a host array by the host encoder (tiffio.write_tiff); the two write the same file.  timing gains
-    write_seconds and file_bytes."""
+    write_seconds and file_bytes.  tile / overviews ("mode" | "average" | "nearest"; needs compress="lzw"): square LZW tiles and the overview
+    pyramid behind the full-resolution image (tiffio.TileWriter), built and encoded by whichever of the two writers applies."""
     t0 = time.perf_counter()
     if isinstance(data, torch.Tensor) and data.is_cuda and compress is not None:
         from unet_amd.tiffenc import write_tiff_device
         t = data
         if class_zero and not t.dtype.is_floating_point and t.dtype != torch.bool:
             t = t - 1 if t.dtype.is_signed else (t.to(torch.int16) - 1)          # the dtypes of the host path below
-        write_tiff_device(output_file, t, geotransform=geotrans, tags=tags, nodata=nodata, compress=compress, predictor=predictor)
+        write_tiff_device(output_file, t, geotransform=geotrans, tags=tags, nodata=nodata, compress=compress, predictor=predictor,
+                          tile=tile, overviews=overviews)
     else:
         a = data.cpu().numpy() if isinstance(data, torch.Tensor) else np.asarray(data)
         if class_zero and a.dtype.kind in "ui":
             a = a - 1 if a.dtype.kind == "i" else (a.astype(np.int16) - 1)
-        write_tiff(output_file, a, geotransform=geotrans, tags=tags, nodata=nodata, compress=compress, predictor=predictor)
+        write_tiff(output_file, a, geotransform=geotrans, tags=tags, nodata=nodata, compress=compress, predictor=predictor, tile=tile,
+                   overviews=overviews)
     if timing is not None:
         timing.update(write_seconds=time.perf_counter() - t0, file_bytes=os.path.getsize(output_file))
 
@@ -325,6 +328,20 @@ def _float_output(regression, all_classes, specific_class, large_file) -> bool:
     return bool(regression or ((all_classes or specific_class is not None) and not large_file))
 
 
+def _overviews(overviews, regression, all_classes, specific_class, large_file):
+    """ "auto" -> "mode" for a class mask, "average" for everything else: float probabilities, regression, and the probabilities that
+    large_file stretches into int8 planes"""
+    stretched = bool(large_file and (all_classes or specific_class is not None))
+    return resolve_overviews(overviews, not _float_output(regression, all_classes, specific_class, large_file) and not stretched)
+
+
+def _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file):
+    """tile= / overviews= of the prediction entry points, from the arguments alone -> (tile, resampling of the overviews or None)"""
+    tile, overviews = check_tiling(compress, tile, overviews, auto=True)
+    overviews = _overviews(overviews, regression, all_classes, specific_class, large_file)
+    return check_tiling(compress, tile, overviews, _float_output(regression, all_classes, specific_class, large_file))
+
+
 def _want(regression, all_classes, specific_class):
     if regression:
         return 0                                      # the single band
@@ -369,7 +386,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                    regression: bool = False, all_classes: bool = False, specific_class: Optional[int] = None, large_file: bool = False,
                    batch_size: int = 16, out_path=None, class_zero: bool = False, timing: Optional[dict] = None,
                    batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
-                   return_array: bool = True):
+                   return_array: bool = True, tile=None, overviews=None):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -397,6 +414,12 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
              array is encoded on the device where it was assembled there (one rank, RCCL ranks) and only the compressed bytes reach the
              host; the int8 large_file merge and gloo ranks, which assemble on the host, use the host encoder -- the same file either way.
              timing gains write_seconds and file_bytes
+    tile     None | a multiple of 16 in 16..1024 (256 is the usual choice; needs compress="lzw"): out_path is written as square LZW tiles
+             instead of strips (tiffio.TileWriter)
+    overviews  None | "auto" | "mode" | "average" | "nearest" (needs tile): the overview pyramid is written behind the full-resolution image,
+             each level from the one before it down to the first that fits one tile -- a cloud-optimised GeoTIFF.  "auto": "mode" for a
+             class mask, "average" for float probabilities, regression and the int8 large_file planes; "mode" on float outputs is refused.
+             The pyramid is built and encoded on the device wherever the merged array is encoded there
     return_array  False (needs out_path): nothing is returned, and with compress="lzw" the merged array never goes to the host
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
@@ -404,6 +427,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     check_blend(blend, large_file)
     post = check_postprocess(postprocess, regression, all_classes, specific_class)
     check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
+    tile, overviews = _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file)
     if not return_array and out_path is None:
         raise ValueError("return_array=False needs out_path: the prediction would go nowhere")
     model = getattr(model, "model", model)
@@ -451,7 +475,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                          codes, blend, post, keep_out)
     if rank == 0 and out_path is not None:
         ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
-        store_tif(out_path, out, ogt, tags, -9999 if regression else None, class_zero, compress, predictor, timing)
+        store_tif(out_path, out, ogt, tags, -9999 if regression else None, class_zero, compress, predictor, timing, tile, overviews)
     if timing is not None:
         timing.update(kept_windows=len(wins), all_windows=int(len(keep)), mosaic=(MH, MW))
     if rank != 0 or not return_array:
@@ -609,7 +633,8 @@ def _tile_windows(batch_size: int, device, div255_twice: bool) -> Callable:
 
 def save_predictions(predict_model, predict_path, regression, merge=False, all_classes=False, specific_class=None, large_file=False,
                      AOI=None, year=None, validation_vision=True, class_zero=False, batch_size=16, timing: Optional[dict] = None,
-                     batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1):
+                     batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
+                     tile=None, overviews=None):
     """tta: None | "flips" | "d4" | a tuple of D4 codes (see predict_raster and unet_amd/tta.py), merged and per-tile outputs alike.
     blend: "mean" | "gaussian" (see predict_raster): how the windows of a merged prediction combine; only with merge=True (per-tile
     outputs have no overlap) and not with large_file (ValueError before the model is loaded).
@@ -617,10 +642,13 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     before the model is loaded).
     compress / predictor: None | "lzw", 1 | 2 (see predict_raster).  The merged raster is encoded where the merge assembled it (on the
     device with one rank or RCCL); per-tile outputs (merge=False) use the host encoder.
+    tile / overviews (see predict_raster): tiles and the overview pyramid of the MERGED raster only; per-tile outputs (merge=False) ignore
+    them, as a tile is one block anyway.
     validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
     check_blend(blend, large_file, merge)
     post = check_postprocess(postprocess, regression, all_classes, specific_class, merge)
     check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
+    tile, overviews = _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file)
     rank, local_rank, world = _dist_ctx()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model
@@ -654,7 +682,7 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     if rank != 0:
         return None
     name = "_".join(filter(None, [AOI, year, model_name, "prediction"])) + ".tif"
-    store_tif(output_folder / name, out, gt, geos[0][1], -9999 if regression else None, class_zero, compress, predictor, timing)
+    store_tif(output_folder / name, out, gt, geos[0][1], -9999 if regression else None, class_zero, compress, predictor, timing, tile, overviews)
     print(f"Prediction stored in {output_folder}.")
     return output_folder if regression else output_folder / name
 

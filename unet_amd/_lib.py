@@ -116,6 +116,14 @@ class ElasticImage(C.Structure):
     _fields_ = [("key0", C.c_uint32), ("key1", C.c_uint32), ("alpha", C.c_float), ("fired", C.c_int32), ("same_dxdy", C.c_int32)]
 
 
+class TiffLevel(C.Structure):
+    """unet_tiff_level: one image of a launch over tiles (include/unet_hip.h)"""
+    _fields_ = [("src", vp), ("row_stride", C.c_longlong), ("plane_stride", C.c_longlong), ("H", C.c_int), ("W", C.c_int)]
+
+
+TIFF_MAX_LEVELS = 32
+
+
 class PackJob(C.Structure):
     _fields_ = [("w", vp), ("wp", vp), ("Cout", C.c_int), ("Cin", C.c_int), ("ks", C.c_int), ("mode", C.c_int), ("out_scale", vp)]
 
@@ -218,6 +226,9 @@ _sig = {
     "unet_tiff_lzw_encode": (ll, [vp, ll, vp, ll]),
     "unet_tiff_encode_strips": (i, [vp, i, i, i, i, ll, ll, i, i, ll, i, vp, ll, vp, vp]),
     "unet_tiff_compact_strips": (i, [vp, ll, vp, vp, i, vp, ll, vp]),
+    "unet_tiff_encode_tiles": (i, [vp, i, i, i, i, ll, ll, i, i, ll, i, vp, ll, vp, vp]),
+    "unet_tiff_encode_tile_levels": (i, [C.POINTER(TiffLevel), i, i, i, i, i, ll, i, vp, ll, vp, vp]),
+    "unet_tiff_reduce_level": (i, [vp, i, i, i, i, i, ll, ll, i, i, C.c_double, vp, vp]),
     "unet_mosaic_finalize_rows": (i, [vp, vp, i, i, i, i, i, vp, c_float_p, vp]),
     "unet_tiles_stage": (i, [vp, i, i, i, i, i, i, C.c_ulonglong, C.c_ulonglong, vp, vp]),
     "unet_mask_stage": (i, [vp, i, i, i, i, C.c_ulonglong, C.c_ulonglong, vp, i, vp]),

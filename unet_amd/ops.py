@@ -1501,6 +1501,79 @@ def tiff_compact_strips(scratch: torch.Tensor, slot: int, sizes: torch.Tensor, o
                                        _stream()), what)
 
 
+def tiff_encode_tiles(img, tile: int, predictor: int, first: int, count: int, scratch: torch.Tensor, sizes: torch.Tensor):
+    """LZW-encodes tiles [first, first + count) of img [P, H, W] (as tiff_encode_strips takes it) in TIFF tile order -- plane-major, tile
+    rows, tile columns; samples beyond the right / bottom edge are zero -- into scratch (uint8, count slots of
+    tiff_slot_bytes(tile * tile * element size)) and their byte counts into sizes (int32 [count], read as unsigned).
+    img may be a list of such images of one dtype and plane count (the levels of a pyramid): the tiles are then numbered through the
+    list, one image after the other, and one launch encodes tiles of several images."""
+    what = "tiff_encode_tiles"
+    imgs = list(img) if isinstance(img, (list, tuple)) else [img]
+    if not 1 <= len(imgs) <= L.TIFF_MAX_LEVELS:
+        raise ValueError(f"{what}: 1..{L.TIFF_MAX_LEVELS} images, got {len(imgs)}")
+    if isinstance(tile, bool) or not isinstance(tile, int) or not 16 <= tile <= 1024 or tile % 16:
+        raise ValueError(f"{what}: tile must be a multiple of 16 in 16..1024, got {tile!r}")
+    table, total = (L.TiffLevel * len(imgs))(), 0
+    for k, t in enumerate(imgs):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() != 3 or t.element_size() not in (1, 2, 4) or t.is_complex():
+            raise ValueError(f"{what}: img must be a [P, H, W] GPU tensor of 1-, 2- or 4-byte samples")
+        P, H, W = (int(v) for v in t.shape)
+        if min(P, H, W) < 1 or t.stride(2) != 1 or t.stride(1) < W or (P > 1 and t.stride(0) < 1):
+            raise ValueError(f"{what}: img {tuple(t.shape)} with strides {t.stride()}: rows must be contiguous and the strides positive")
+        if t.dtype != imgs[0].dtype or P != imgs[0].shape[0] or t.device != imgs[0].device:
+            raise ValueError(f"{what}: the images must share dtype, plane count and device")
+        table[k] = L.TiffLevel(t.data_ptr(), t.stride(1), t.stride(0) if P > 1 else H * t.stride(1), H, W)
+        total += P * -(-H // tile) * -(-W // tile)
+    t0 = imgs[0]
+    es = t0.element_size()
+    if predictor not in (1, 2) or (predictor == 2 and t0.dtype.is_floating_point):
+        raise ValueError(f"{what}: predictor must be 1, or 2 on integer samples (got {predictor!r} on {t0.dtype})")
+    if not (0 <= first and 1 <= count and first + count <= total):
+        raise ValueError(f"{what}: tiles [{first}, {first + count}) of {total}")
+    slot = tiff_slot_bytes(tile * tile * es)
+    _pp_tensor(what, "scratch", scratch, torch.uint8)
+    _pp_tensor(what, "sizes", sizes, torch.int32)
+    if scratch.numel() < count * slot or sizes.numel() < count or scratch.device != t0.device or sizes.device != t0.device:
+        raise ValueError(f"{what}: scratch needs {count * slot} bytes and sizes {count} entries on {t0.device}")
+    check(lib.unet_tiff_encode_tile_levels(table, len(imgs), es, int(t0.shape[0]), tile, predictor, first, count, scratch.data_ptr(), slot,
+                                           sizes.data_ptr(), _stream()), what)
+    return slot
+
+
+TIFF_RESAMPLINGS = {"nearest": 0, "mode": 1, "average": 2}
+
+
+def tiff_reduce_level(img: torch.Tensor, resampling: str, nodata, out: torch.Tensor):
+    """out [P, ceil(H / 2), ceil(W / 2)] (contiguous, img's dtype) = the next overview level of img [P, H, W] (as tiff_encode_strips takes
+    it) by the pyramid rule of unet_amd/tiffenc.py.  nodata: None, or the value whose samples do not count (NaN for float samples: NaN
+    samples); a value no sample of an integer type can equal leaves every sample valid."""
+    what = "tiff_reduce_level"
+    kinds = {torch.uint8: 0, torch.uint16: 0, torch.int8: 1, torch.int16: 1, torch.int32: 1, torch.float32: 2}
+    if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dim() != 3 or img.dtype not in kinds:
+        raise ValueError(f"{what}: img must be a [P, H, W] GPU tensor of 8 / 16 / 32-bit integers or float32")
+    P, H, W = (int(v) for v in img.shape)
+    if min(P, H, W) < 1 or max(H, W) < 2 or img.stride(2) != 1 or img.stride(1) < W or (P > 1 and img.stride(0) < 1):
+        raise ValueError(f"{what}: img {tuple(img.shape)} with strides {img.stride()}: larger than 1 x 1, rows contiguous, strides positive")
+    if resampling not in TIFF_RESAMPLINGS or (resampling == "mode" and img.dtype.is_floating_point):
+        raise ValueError(f"{what}: resampling must be 'nearest', 'average' or (integer samples) 'mode', got {resampling!r} on {img.dtype}")
+    h, w = -(-H // 2), -(-W // 2)
+    _pp_tensor(what, "out", out, img.dtype, numel=P * h * w)
+    if tuple(out.shape) != (P, h, w) or out.device != img.device:
+        raise ValueError(f"{what}: out must be [{P}, {h}, {w}] on {img.device}, got {tuple(out.shape)} on {out.device}")
+    has, nd = 0, 0.0
+    if nodata is not None:
+        nd = float(nodata)
+        if img.dtype.is_floating_point:
+            has = 1
+        else:
+            info = torch.iinfo(img.dtype)
+            has = int(nd == nd and nd == int(nd) and info.min <= int(nd) <= info.max)
+    check(lib.unet_tiff_reduce_level(img.data_ptr(), img.element_size(), kinds[img.dtype], P, H, W, img.stride(1),
+                                     img.stride(0) if P > 1 else H * img.stride(1), TIFF_RESAMPLINGS[resampling], has, nd if has else 0.0,
+                                     out.data_ptr(), _stream()), what)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- border distance and weight map (csrc/edt.hip)
 
 EDT_MAX_SIDE = 8192          # 2 * 8191^2 < 2^31: the squared distance fits int32

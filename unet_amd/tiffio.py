@@ -31,24 +31,41 @@ def _dtype(bits: int, fmt: int, bo: str) -> np.dtype:
     return np.dtype(f"{bo}{kind}{bits // 8}")
 
 
-def _parse_tags(b, path):
-    """IFD 0 of a TIFF (classic: magic 42, 32-bit offsets; BigTIFF: magic 43, 64-bit offsets and counts) held in a bytes-like object
-    (bytes or mmap): {tag: values}, byte-order prefix"""
+def _header(b, path):
+    """(offset of IFD 0, BigTIFF?, byte-order prefix) of a TIFF: classic (magic 42, 32-bit offsets) or BigTIFF (magic 43, 64-bit)"""
     bo = {b"II": "<", b"MM": ">"}[bytes(b[:2])]
     magic = struct.unpack(bo + "H", b[2:4])[0]
     if magic == 42:
-        off = struct.unpack(bo + "I", b[4:8])[0]
-        n = struct.unpack(bo + "H", b[off:off + 2])[0]
-        base, esz, cfmt, inl = off + 2, 12, "I", 4
-    elif magic == 43:
+        return struct.unpack(bo + "I", b[4:8])[0], False, bo
+    if magic == 43:
         osz, zero = struct.unpack(bo + "HH", b[4:8])
         if osz != 8 or zero != 0:
             raise NotImplementedError(f"{path}: BigTIFF with offset size {osz}")
-        off = struct.unpack(bo + "Q", b[8:16])[0]
+        return struct.unpack(bo + "Q", b[8:16])[0], True, bo
+    raise NotImplementedError(f"{path}: not a TIFF (magic {magic})")
+
+
+def _parse_tags(b, path, level: int = 0):
+    """IFD `level` of a TIFF held in a bytes-like object (bytes or mmap): {tag: values}, byte-order prefix.  level 0 reads the first IFD
+    alone; a higher level walks the chain (_ifd_offsets)."""
+    off, big, bo = _header(b, path)
+    if level:
+        offs = _ifd_offsets(b, path, off, big, bo)
+        if level >= len(offs):
+            raise ValueError(f"{path}: level {level} of a file with {len(offs)} image(s)")
+        off = offs[level]
+    return _parse_ifd(b, path, off, big, bo), bo
+
+
+def _parse_ifd(b, path, off: int, big: bool, bo: str) -> Dict[int, tuple]:
+    if big:
         n = struct.unpack(bo + "Q", b[off:off + 8])[0]
         base, esz, cfmt, inl = off + 8, 20, "Q", 8
     else:
-        raise NotImplementedError(f"{path}: not a TIFF (magic {magic})")
+        n = struct.unpack(bo + "H", b[off:off + 2])[0]
+        base, esz, cfmt, inl = off + 2, 12, "I", 4
+    if base + esz * n > len(b):
+        raise ValueError(f"{path}: the IFD at offset {off} holds {n} entries: past the end of the file ({len(b)} bytes)")
     tags: Dict[int, tuple] = {}
     for i in range(n):
         e = bytes(b[base + esz * i: base + esz * (i + 1)])
@@ -69,7 +86,28 @@ def _parse_tags(b, path):
             tags[tag] = (data.rstrip(b"\0").decode("latin1"),)
         else:
             tags[tag] = struct.unpack(bo + fmt[0] * (cnt * len(fmt)), data)
-    return tags, bo
+    return tags
+
+
+def _ifd_offsets(b, path, first: int, big: bool, bo: str):
+    """the offsets of the chained IFDs, first to last.  The chain is user data: an IFD (its count, entries and next pointer) must lie
+    inside the file, and an offset that was already visited -- a cycle -- is refused.  Every IFD takes at least 6 bytes of its own, so
+    the walk ends after at most len(b) / 6 steps."""
+    cnt_fmt, cnt_sz, esz, nxt_fmt, nxt_sz = ("Q", 8, 20, "Q", 8) if big else ("H", 2, 12, "I", 4)
+    offs, seen, off = [], set(), first
+    while off:
+        if off in seen:
+            raise ValueError(f"{path}: the IFD chain returns to offset {off}: a cycle")
+        if off + cnt_sz > len(b):
+            raise ValueError(f"{path}: IFD {len(offs)} at offset {off} lies past the end of the file ({len(b)} bytes)")
+        n = struct.unpack(bo + cnt_fmt, b[off:off + cnt_sz])[0]
+        end = off + cnt_sz + esz * n
+        if end + nxt_sz > len(b):
+            raise ValueError(f"{path}: IFD {len(offs)} at offset {off} holds {n} entries: past the end of the file ({len(b)} bytes)")
+        seen.add(off)
+        offs.append(off)
+        off = struct.unpack(bo + nxt_fmt, b[end:end + nxt_sz])[0]
+    return offs
 
 
 _codec_lib = None
@@ -213,9 +251,9 @@ def _one_error_contract(fn):
     import zlib
 
     @functools.wraps(fn)
-    def reader(path):
+    def reader(path, *args):
         try:
-            return fn(path)
+            return fn(path, *args)
         except (ValueError, NotImplementedError, OSError):
             raise
         except (KeyError, IndexError, struct.error, zlib.error, MemoryError, ArithmeticError, TypeError, UnicodeError) as e:
@@ -237,11 +275,34 @@ def tiff_info(path) -> Dict:
 
 
 @_one_error_contract
+def tiff_levels(path) -> list:
+    """One {"height", "width", "subfile_type"} per IFD of the file, in chain order: the full-resolution image first, then the overviews
+    a tiled writer placed behind it (NewSubfileType 1), largest first.  Header-only, memory-mapped."""
+    import mmap
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as b:
+        off, big, bo = _header(b, path)
+        out = [_parse_ifd(b, path, o, big, bo) for o in _ifd_offsets(b, path, off, big, bo)]
+    return [{"height": t[257][0], "width": t[256][0], "subfile_type": t.get(254, (0,))[0]} for t in out]
+
+
 def read_tiff(path) -> Tuple[np.ndarray, Dict]:
     """Returns (array [C,H,W] (or [H,W] for one band), meta) with meta['geotransform'] = (ulx, xres, 0, uly, 0, -yres)
     when the file is georeferenced and meta['tags'] holding the raw GeoTIFF tags.  The file is memory-mapped (copy-on-write), never slurped:
     an uncompressed native-endian file with contiguous strips comes back as a VIEW of the mapping (no copy at all: the training feed's one
     copy is the one into its pinned staging buffer); everything else is decoded strip by strip into one output array."""
+    return _read_ifd(path, 0)
+
+
+def read_tiff_level(path, level: int) -> np.ndarray:
+    """The array of IFD `level` of the file (0: the full-resolution image, what read_tiff returns; 1...: the overviews, see tiff_levels),
+    through the decoders and the error contract of read_tiff."""
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level < 0:
+        raise ValueError(f"level must be an int >= 0, got {level!r}")
+    return _read_ifd(path, int(level))[0]
+
+
+@_one_error_contract
+def _read_ifd(path, level):
     import mmap
     import os
     with open(path, "rb") as f:
@@ -250,7 +311,7 @@ def read_tiff(path) -> Tuple[np.ndarray, Dict]:
         else:
             mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_COPY)
     b = np.frombuffer(mm, dtype=np.uint8)           # (keeps the mapping alive for as long as a view of it exists)
-    tags, bo = _parse_tags(mm, path)
+    tags, bo = _parse_tags(mm, path, level)
     W, H = tags[256][0], tags[257][0]
     spp = tags.get(277, (1,))[0]
     bits = tags.get(258, (1,))[0]
@@ -379,6 +440,77 @@ def _samples(arr) -> np.ndarray:
     return a
 
 
+def _geo_dict(tags, geotransform, nodata) -> Dict[int, tuple]:
+    """the georeferencing tags of a writer: the caller's tags, ModelPixelScale / ModelTiepoint of the geotransform, GDAL_NODATA"""
+    geo = dict(tags or {})
+    if geotransform is not None:
+        ulx, xres, _, uly, _, yres = geotransform
+        geo[33550] = (abs(xres), abs(yres), 0.0)
+        geo[33922] = (0.0, 0.0, 0.0, ulx, uly, 0.0)
+    if nodata is not None:
+        geo[42113] = (str(nodata),)
+    return geo
+
+
+def _image_specs(W: int, H: int, C: int, dtype: np.dtype, predictor: int) -> list:
+    """(tag, type, values) of what every LZW image of the writers states, strips or tiles, full resolution or overview: size, samples,
+    Compression 5, band-sequential planes (PlanarConfiguration 2 for C > 1), Predictor, ExtraSamples, SampleFormat"""
+    specs = [(256, 4, [W]), (257, 4, [H]), (258, 3, [dtype.itemsize * 8] * C), (259, 3, [5]), (262, 3, [1]), (277, 3, [C]),
+             (284, 3, [2 if C > 1 else 1]), (339, 3, [{"u": 1, "i": 2, "f": 3}[dtype.kind]] * C)]
+    if predictor == 2:
+        specs.append((317, 3, [2]))
+    if C > 1:
+        specs.append((338, 3, [0] * (C - 1)))
+    return specs
+
+
+def _geo_specs(geo: Dict[int, tuple]) -> list:
+    out = []
+    for t in sorted(geo):
+        v = geo[t]
+        if t in (34737, 42113):
+            out.append((t, 2, v[0] if isinstance(v, tuple) else v))
+        elif t == 34735:
+            out.append((t, 3, list(v)))
+        else:
+            out.append((t, 12, list(v)))
+    return out
+
+
+def _tag_entries(specs) -> list:
+    """(tag, type, values) -> (tag, type, count, little-endian payload), sorted by tag as an IFD must be"""
+    entries = []
+    for tag, typ, vals in specs:
+        if typ == 2:
+            payload = vals.encode("latin1") + b"\0"
+            cnt = len(payload)
+        else:
+            payload = struct.pack("<" + _TYPES[typ][0][0] * len(vals), *vals)
+            cnt = len(vals)
+        entries.append((tag, typ, cnt, payload))
+    entries.sort(key=lambda e: e[0])
+    return entries
+
+
+def _pack_ifd(entries, ifd_off: int, big: bool, next_ifd: int = 0) -> bytes:
+    """one IFD placed at ifd_off: entry count, entries, the offset of the next IFD, then the values that do not fit an entry (each on a
+    word boundary).  Its length depends on the tags' types and counts alone, not on their values."""
+    off_fmt, inl = ("Q", 8) if big else ("I", 4)
+    n = len(entries)
+    extra_off = ifd_off + (8 + 20 * n + 8 if big else 2 + 12 * n + 4)
+    extra, body = b"", b""
+    for tag, typ, cnt, payload in entries:
+        if len(payload) <= inl:
+            val = payload.ljust(inl, b"\0")
+        else:
+            if len(extra) % 2:
+                extra += b"\0"
+            val = struct.pack("<" + off_fmt, extra_off + len(extra))
+            extra += payload
+        body += struct.pack("<HH" + off_fmt, tag, typ, cnt) + val
+    return struct.pack("<Q" if big else "<H", n) + body + struct.pack("<" + off_fmt, next_ifd) + extra
+
+
 class StripWriter:
     """The file layout of compress="lzw", filled strip by strip by whoever encodes (write_tiff below: the host encoder; unet_amd/tiffenc.py:
     the device).  Little-endian; LZW strips of rows_per_strip rows (default: the largest row count whose strip is at most 64 KiB, at
@@ -407,13 +539,7 @@ class StripWriter:
         self.strips = [(p, s * rps, min(rps, H - s * rps)) for p in range(C) for s in range(spp)]          # (band, first row, rows) in file order
         worst = sum(lzw_cap(rows * W * es) for _, _, rows in self.strips[:spp]) * C
         self.big = (worst > (1 << 32) - (1 << 20)) if bigtiff is None else bool(bigtiff)
-        self.geo = dict(tags or {})
-        if geotransform is not None:
-            ulx, xres, _, uly, _, yres = geotransform
-            self.geo[33550] = (abs(xres), abs(yres), 0.0)
-            self.geo[33922] = (0.0, 0.0, 0.0, ulx, uly, 0.0)
-        if nodata is not None:
-            self.geo[42113] = (str(nodata),)
+        self.geo = _geo_dict(tags, geotransform, nodata)
         self.offsets, self.counts = [], []
         self.f = open(path, "wb")
         self.f.write(b"II" + (struct.pack("<HHHQ", 43, 8, 0, 0) if self.big else struct.pack("<HI", 42, 0)))
@@ -439,56 +565,266 @@ class StripWriter:
         if not big and self.pos > (1 << 32) - (1 << 20):
             self.f.close()
             raise ValueError("the compressed data does not fit a classic TIFF's 32-bit offsets: pass bigtiff=None or True")
-        off_t, off_fmt, inl = (16, "Q", 8) if big else (4, "I", 4)
-        kind = {"u": 1, "i": 2, "f": 3}[self.dtype.kind]
-        entries = []          # (tag, type, count, payload-bytes)
-
-        def add(tag, typ, vals):
-            if typ == 2:
-                payload = vals.encode("latin1") + b"\0"
-                cnt = len(payload)
-            else:
-                payload = struct.pack("<" + _TYPES[typ][0][0] * len(vals), *vals)
-                cnt = len(vals)
-            entries.append((tag, typ, cnt, payload))
-
-        add(256, 4, [self.W]); add(257, 4, [self.H]); add(258, 3, [self.dtype.itemsize * 8] * C); add(259, 3, [5])
-        add(262, 3, [1]); add(273, off_t, self.offsets); add(277, 3, [C]); add(278, 4, [self.rows_per_strip]); add(279, off_t, self.counts)
-        add(284, 3, [2 if C > 1 else 1])
-        if self.predictor == 2:
-            add(317, 3, [2])
-        if C > 1:
-            add(338, 3, [0] * (C - 1))
-        add(339, 3, [kind] * C)
-        for t in sorted(self.geo):
-            v = self.geo[t]
-            if t in (34737, 42113):
-                add(t, 2, v[0] if isinstance(v, tuple) else v)
-            elif t == 34735:
-                add(t, 3, list(v))
-            else:
-                add(t, 12, list(v))
-        entries.sort(key=lambda e: e[0])
+        off_t = 16 if big else 4
+        specs = _image_specs(self.W, self.H, C, self.dtype, self.predictor)
+        specs += [(273, off_t, self.offsets), (278, 4, [self.rows_per_strip]), (279, off_t, self.counts)] + _geo_specs(self.geo)
         pad = self.pos % 2                                          # an IFD starts on a word boundary
         ifd_off = self.pos + pad
-        n = len(entries)
-        extra_off = ifd_off + (8 + 20 * n + 8 if big else 2 + 12 * n + 4)
-        extra, body = b"", b""
-        for tag, typ, cnt, payload in entries:
-            if len(payload) <= inl:
-                val = payload.ljust(inl, b"\0")
-            else:
-                if len(extra) % 2:
-                    extra += b"\0"
-                val = struct.pack("<" + off_fmt, extra_off + len(extra))
-                extra += payload
-            body += struct.pack("<HH" + off_fmt, tag, typ, cnt) + val
-        self.f.write(b"\0" * pad + struct.pack("<Q" if big else "<H", n) + body + struct.pack("<" + off_fmt, 0) + extra)
+        self.f.write(b"\0" * pad + _pack_ifd(_tag_entries(specs), ifd_off, big))
         size = self.f.tell()
         self.f.seek(8 if big else 4)
-        self.f.write(struct.pack("<" + off_fmt, ifd_off))
+        self.f.write(struct.pack("<Q" if big else "<I", ifd_off))
         self.f.close()
         return size
+
+
+RESAMPLINGS = ("mode", "average", "nearest")
+
+
+def check_tiling(compress, tile, overviews, floats: bool = False, auto: bool = False):
+    """the tile= / overviews= arguments of the writers, validated from the arguments alone -> (tile, overviews).  auto: "auto" is accepted
+    (the prediction entry points resolve it with resolve_overviews)."""
+    if tile is None:
+        if overviews is not None:
+            raise ValueError(f"overviews={overviews!r} needs tile=: overviews are written into tiled files only")
+        return None, None
+    if isinstance(tile, bool) or not isinstance(tile, (int, np.integer)) or not 16 <= tile <= 1024 or tile % 16:
+        raise ValueError(f"tile must be None or a multiple of 16 in 16..1024, got {tile!r}")
+    if compress != "lzw":
+        raise ValueError("tile= needs compress='lzw': uncompressed tiled files are not written")
+    if overviews is not None and overviews not in RESAMPLINGS and not (auto and overviews == "auto"):
+        raise ValueError(f"overviews must be None, {', '.join(repr(r) for r in RESAMPLINGS)}{' or auto' if auto else ''}: got {overviews!r}")
+    if overviews == "mode" and floats:
+        raise ValueError("overviews='mode' counts equal values: it is for class masks and integer samples, not for float samples")
+    return int(tile), overviews
+
+
+def resolve_overviews(overviews, class_mask: bool):
+    """ "auto" -> "mode" for a class mask, "average" for everything else (probabilities, regression, the int8 stretch)"""
+    return ("mode" if class_mask else "average") if overviews == "auto" else overviews
+
+
+def overview_shapes(H: int, W: int, tile: int) -> list:
+    """[(H_1, W_1), (H_2, W_2), ...]: level k + 1 has ceil(H_k / 2) x ceil(W_k / 2) samples and levels are added while
+    max(H_k, W_k) > tile, so the last one fits one tile; a raster no larger than a tile has none"""
+    out = []
+    while max(H, W) > tile:
+        H, W = -(-H // 2), -(-W // 2)
+        out.append((H, W))
+    return out
+
+
+def nodata_sample(nodata, dtype):
+    """`nodata` as a sample of `dtype`, or None when no sample can equal it (none given; not a whole number or out of range for an
+    integer type) -- then every sample is valid.  Float samples are compared with float32(nodata)."""
+    dtype = np.dtype(dtype)
+    if nodata is None:
+        return None
+    nd = float(nodata)
+    if dtype.kind == "f":
+        return dtype.type(nd)
+    if nd != nd or nd != int(nd) or not np.iinfo(dtype).min <= int(nd) <= np.iinfo(dtype).max:
+        return None
+    return dtype.type(int(nd))
+
+
+def reduce_level(a: np.ndarray, resampling: str, nodata=None) -> np.ndarray:
+    """The next overview level of [C, H, W] samples, [C, ceil(H / 2), ceil(W / 2)] -- the pyramid rule of unet_amd/tiffenc.py (module
+    docstring) for host arrays; csrc/tiff_pyramid.hip computes the same samples on the device."""
+    if resampling not in RESAMPLINGS:
+        raise ValueError(f"resampling must be one of {RESAMPLINGS}, got {resampling!r}")
+    if resampling == "mode" and a.dtype.kind == "f":
+        raise ValueError("resampling 'mode' is not for float samples")
+    C, H, W = a.shape
+    h, w = -(-H // 2), -(-W // 2)
+    nd = nodata_sample(nodata, a.dtype)
+    if resampling == "nearest":
+        return np.ascontiguousarray(a[:, ::2, ::2])
+    v, m = [], []                                            # the block in row-major order (TL, TR, BL, BR) and which of it counts
+    for dy in (0, 1):
+        for dx in (0, 1):
+            s = np.zeros((C, h, w), a.dtype)
+            inside = np.zeros((C, h, w), bool)
+            part = a[:, dy::2, dx::2]
+            s[:, :part.shape[1], :part.shape[2]] = part
+            inside[:, :part.shape[1], :part.shape[2]] = True
+            if nd is not None:
+                inside &= ~np.isnan(s) if nd != nd else (s != nd)
+            v.append(s)
+            m.append(inside)
+    n = m[0].astype(np.int64) + m[1] + m[2] + m[3]
+    fill = a.dtype.type(0) if nd is None else nd              # (n == 0 needs a nodata: without one the top-left sample always counts)
+    if resampling == "average":
+        if a.dtype.kind == "f":
+            acc = np.zeros((C, h, w), np.float32)
+            for s, ok in zip(v, m):
+                acc = np.where(ok, acc + s, acc)              # sequential fp32 sum in row-major order
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out = acc / n.astype(np.float32)
+        else:
+            tot = sum(np.where(ok, s.astype(np.int64), 0) for s, ok in zip(v, m))
+            out = (2 * tot + n) // np.maximum(2 * n, 1)        # round half up; // floors, so negative means round the same way
+        return np.where(n > 0, out, fill).astype(a.dtype)
+    best, best_n = np.full((C, h, w), fill, a.dtype), np.zeros((C, h, w), np.int64)
+    for k in range(4):
+        cnt = sum((m[k] & m[j] & (v[j] == v[k])).astype(np.int64) for j in range(4))
+        take = cnt > best_n                                   # strictly more: a tie stays with the value that came first
+        best, best_n = np.where(take, v[k], best), np.where(take, cnt, best_n)
+    return best
+
+
+def build_overviews(a: np.ndarray, tile: int, resampling: str, nodata=None) -> list:
+    """the overview levels of [C, H, W] samples, each computed from the one before it"""
+    out = []
+    for _ in overview_shapes(a.shape[1], a.shape[2], tile):
+        a = reduce_level(a, resampling, nodata)
+        out.append(a)
+    return out
+
+
+class TileWriter:
+    """The tiled layout of compress="lzw" with tile=: square LZW tiles of `tile` samples a side, band-sequential, and -- with
+    levels beyond the first -- the overview images of a cloud-optimised GeoTIFF.  Header, then ALL IFDs (IFD 0: full resolution with the
+    georeferencing tags; then one IFD per overview in decreasing size with NewSubfileType 1, its own tile arrays and the same sample,
+    Predictor and GDAL_NODATA tags), then the tile data: the smallest overview first, the full resolution last; within a level tile
+    k = (p * tiles_down + j) * tiles_across + i.  The tile counts are known before anything is encoded, so the IFD block has a known size:
+    it is reserved on open and written with the real TileOffsets / TileByteCounts by close().  BigTIFF is chosen from the worst case
+    (every tile at its capacity).  Edge tiles are whole tiles, padded with zeros by whoever encodes them.  The GDAL ghost area and the
+    per-tile leader / trailer bytes, both optional in the COG specification, are not written."""
+
+    def __init__(self, path, C: int, shapes, dtype, tile: int, predictor: int = 1, geotransform=None, tags: Optional[Dict[int, tuple]] = None,
+                 nodata=None, bigtiff: Optional[bool] = None):
+        self.dtype = np.dtype(dtype)
+        if self.dtype.kind not in "uif" or self.dtype.itemsize not in (1, 2, 4) or (self.dtype.kind == "f" and self.dtype.itemsize != 4):
+            raise ValueError(f"compress='lzw': {self.dtype} samples are not written (8 / 16 / 32-bit integers and float32 are)")
+        check_compress("lzw", predictor, self.dtype.kind == "f")
+        check_tiling("lzw", tile, None)
+        self.shapes = [(int(h), int(w)) for h, w in shapes]          # level 0 first
+        if C < 1 or not self.shapes or min(min(s) for s in self.shapes) < 1:
+            raise ValueError(f"compress='lzw': empty image {C} x {self.shapes}")
+        self.C, self.tile, self.predictor = C, int(tile), predictor
+        self.grid = [(-(-h // tile), -(-w // tile)) for h, w in self.shapes]          # (tiles down, tiles across) of a level
+        self.per_level = [C * ty * tx for ty, tx in self.grid]
+        self.order = tuple(range(len(self.shapes) - 1, -1, -1))                     # levels in file order: smallest first
+        self._open = list(self.order)                                               # levels that still take tiles
+        self.slot_cap = lzw_cap(tile * tile * self.dtype.itemsize)
+        self.geo = _geo_dict(tags, geotransform, nodata)
+        self.offsets = [[] for _ in self.shapes]
+        self.counts = [[] for _ in self.shapes]
+        self.big = False
+        if bigtiff is None:
+            self.big = len(self._ifds(True)) + sum(self.per_level) * self.slot_cap > (1 << 32) - (1 << 20)
+        else:
+            self.big = bool(bigtiff)
+        self.f = open(path, "wb")
+        head = 16 if self.big else 8
+        self.f.write(b"II" + (struct.pack("<HHHQ", 43, 8, 0, head) if self.big else struct.pack("<HI", 42, head)))
+        self.f.write(self._ifds(True))
+        self.pos = self.f.tell()
+
+    def _ifds(self, reserve: bool) -> bytes:
+        """the block of all IFDs as it stands behind the header (reserve: with zeros for the tile arrays, which has the same length)"""
+        big = self.big
+        off_t = 16 if big else 4
+        pos = 16 if big else 8
+        out = b""
+        for k, (h, w) in enumerate(self.shapes):
+            n = self.per_level[k]
+            specs = _image_specs(w, h, self.C, self.dtype, self.predictor)
+            specs += [(322, 3, [self.tile]), (323, 3, [self.tile]), (324, off_t, [0] * n if reserve else self.offsets[k]),
+                      (325, off_t, [0] * n if reserve else self.counts[k])]
+            if k == 0:
+                specs += _geo_specs(self.geo)
+            else:
+                specs += [(254, 4, [1])] + _geo_specs({t: v for t, v in self.geo.items() if t == 42113})
+            entries = _tag_entries(specs)
+            size = len(_pack_ifd(entries, pos, big))
+            size += size % 2                                                       # the next IFD starts on a word boundary
+            last = k == len(self.shapes) - 1
+            out += _pack_ifd(entries, pos, big, 0 if last else pos + size).ljust(size, b"\0")
+            pos += size
+        return out
+
+    def append(self, data, sizes) -> None:
+        """the next len(sizes) tiles in file order (levels from the smallest to the full resolution, tile order within a level):
+        `data` (bytes-like) holds their streams back to back"""
+        sizes = [int(s) for s in sizes]
+        if sum(sizes) != len(data):
+            raise ValueError(f"TileWriter.append: {len(sizes)} tiles of {sum(sizes)} bytes do not match the data ({len(data)} bytes)")
+        for s in sizes:
+            while self._open and len(self.counts[self._open[0]]) == self.per_level[self._open[0]]:
+                self._open.pop(0)
+            if not self._open:
+                raise ValueError("TileWriter.append: more tiles than the layout holds")
+            self.offsets[self._open[0]].append(self.pos)
+            self.counts[self._open[0]].append(s)
+            self.pos += s
+        self.f.write(data)
+
+    def close(self) -> int:
+        """fills in the reserved IFD block and closes the file -> the file's size in bytes"""
+        if [len(c) for c in self.counts] != self.per_level:
+            self.f.close()
+            raise ValueError(f"TileWriter.close: {[len(c) for c in self.counts]} of {self.per_level} tiles were written")
+        if not self.big and self.pos > (1 << 32) - (1 << 20):
+            self.f.close()
+            raise ValueError("the compressed data does not fit a classic TIFF's 32-bit offsets: pass bigtiff=None or True")
+        size = self.f.tell()
+        self.f.seek(16 if self.big else 8)
+        self.f.write(self._ifds(False))
+        self.f.close()
+        return size
+
+
+def tile_block(a: np.ndarray, p: int, j: int, i: int, tile: int) -> np.ndarray:
+    """tile (p, j, i) of [C, H, W] samples as a whole [tile, tile] block: what lies beyond the right or bottom edge is zero"""
+    part = a[p, j * tile:(j + 1) * tile, i * tile:(i + 1) * tile]
+    if part.shape == (tile, tile):
+        return part
+    block = np.zeros((tile, tile), a.dtype)
+    block[:part.shape[0], :part.shape[1]] = part
+    return block
+
+
+def _lzw_stream(lib, src: np.ndarray, path) -> np.ndarray:
+    cap = lzw_cap(src.size)
+    dst = np.empty(cap, dtype=np.uint8)
+    got = lib.unet_tiff_lzw_encode(src.ctypes.data, src.size, dst.ctypes.data, cap)
+    if got < 0:
+        raise RuntimeError(f"{path}: the LZW encoder overran its capacity of {cap} bytes for a block of {src.size}")
+    return dst[:got]
+
+
+def _write_tiled(path, a: np.ndarray, geotransform, tags, nodata, bigtiff, predictor, tile, overviews) -> int:
+    """write_tiff(compress="lzw", tile=) of host samples: the pyramid by reduce_level, the tiles by unet_tiff_lzw_encode on a thread
+    pool, a batch at a time, appended in file order -- the file does not depend on the thread count.  Predictor 2 runs along the whole
+    padded tile row (the first padded sample holds 0 - last), as libtiff does."""
+    lib = _codecs()
+    levels = [a] + (build_overviews(a, tile, overviews, nodata) if overviews is not None else [])
+    w = TileWriter(path, a.shape[0], [l.shape[1:] for l in levels], a.dtype, tile, predictor, geotransform, tags, nodata, bigtiff)
+    jobs = [(k, p, j, i) for k in w.order for p in range(w.C) for j in range(w.grid[k][0]) for i in range(w.grid[k][1])]
+
+    def encode(job):
+        k, p, j, i = job
+        return _lzw_stream(lib, _predicted_le(tile_block(levels[k], p, j, i, tile), predictor), path)
+
+    try:
+        nthr = _threads()
+        if nthr > 1 and len(jobs) >= 16 and a.nbytes >= (4 << 20):
+            from concurrent.futures import ThreadPoolExecutor
+            step = nthr * 16
+            with ThreadPoolExecutor(max_workers=nthr) as ex:
+                for n in range(0, len(jobs), step):
+                    enc = list(ex.map(encode, jobs[n:n + step]))
+                    w.append(b"".join(e.data for e in enc), [e.size for e in enc])
+        else:
+            for job in jobs:
+                e = encode(job)
+                w.append(e.data, [e.size])
+    except BaseException:
+        w.f.close()
+        raise
+    return w.close()
 
 
 def _predicted_le(block: np.ndarray, predictor: int) -> np.ndarray:
@@ -537,15 +873,24 @@ def _write_lzw(path, a: np.ndarray, geotransform, tags, nodata, bigtiff, predict
 
 
 def write_tiff(path, arr: np.ndarray, geotransform=None, tags: Optional[Dict[int, tuple]] = None, nodata=None, bigtiff: Optional[bool] = None,
-               compress=None, predictor: int = 1, rows_per_strip=None) -> None:
+               compress=None, predictor: int = 1, rows_per_strip=None, tile=None, overviews=None) -> None:
     """Uncompressed, single strip, pixel-interleaved little-endian TIFF of a [C,H,W] or [H,W] array.  bigtiff None: BigTIFF (64-bit offsets)
     when the file would not fit 32-bit offsets -- what GDAL's BIGTIFF=IF_NEEDED does for the reference's outputs (predict.py:19-52): the
     all-classes probabilities of a 20000 x 20000 scene are 8 GB.
     compress="lzw": LZW strips in the layout of StripWriter (band-sequential, IFD behind the data), encoded on the host; predictor=2 adds
-    horizontal differencing (integer samples only); rows_per_strip None: strips of at most 64 KiB."""
-    if compress is not None or predictor != 1 or rows_per_strip is not None:
+    horizontal differencing (integer samples only); rows_per_strip None: strips of at most 64 KiB.
+    tile (a multiple of 16 in 16..1024, needs compress="lzw"): square LZW tiles in the layout of TileWriter instead of strips;
+    overviews "mode" | "average" | "nearest" (needs tile): the overview pyramid of reduce_level behind the full-resolution image, down to
+    the first level that fits one tile -- a cloud-optimised GeoTIFF.  nodata then also marks the samples the overviews leave out."""
+    if compress is not None or predictor != 1 or rows_per_strip is not None or tile is not None or overviews is not None:
         a = _samples(arr)
         check_compress(compress, predictor, a.dtype.kind == "f")
+        tile, overviews = check_tiling(compress, tile, overviews, a.dtype.kind == "f")
+        if tile is not None:
+            if rows_per_strip is not None:
+                raise ValueError("rows_per_strip is for strips: a tiled file (tile=) has none")
+            _write_tiled(path, a, geotransform, tags, nodata, bigtiff, predictor, tile, overviews)
+            return
         if compress is None:
             raise ValueError("rows_per_strip needs compress='lzw': the uncompressed file is one strip")
         _write_lzw(path, a, geotransform, tags, nodata, bigtiff, predictor, rows_per_strip)
