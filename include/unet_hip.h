@@ -745,6 +745,48 @@ int unet_tiff_encode_tile_levels(const unet_tiff_level* levels, int nlevels, int
 int unet_tiff_reduce_level(const void* src, int elem_size, int kind, int P, int H, int W, long long row_stride, long long plane_stride,
                            int resampling, int has_nodata, double nodata, void* dst, void* stream);
 
+/* --------------------------------------------------------- polygon rings --
+ * Ring tracing of a labelled class mask (csrc/vectorize.hip, unet_amd/vectorize.py).  mask / labels are contiguous [H, W] with
+ * H * W <= 2^31 - 1, labels those of unet_cc_label at connectivity 4.  Sides: N=0 W=1 S=2 E=3; the dense id of an edge is 4 p + s, its
+ * compact index offs[p] + popcount(flags[p] & ((1 << s) - 1)).  E edges, R rings, V vertices, all in 1..2^31 - 1.
+ * vec_flags: flags[p] bit s = side s of pixel p is a boundary edge (the neighbour is outside or has another label); 0 where the
+ *   pixel's class has its bit set in exclude8 (256 bits as 8 words, NULL: none).
+ * vec_scan: out[i] = sum over j < i of popcount(in[j] & 15); blocks holds vec_scan_words(n) words, the last one receives the total.
+ * vec_read: copies `count` (1..64) int64 words to the host and waits for the stream: the host reads of a call.
+ * vec_succ: succ[e] = the first existing of left (same pixel, side s + 1), straight (pixel ahead, side s), right (pixel diagonally
+ *   ahead on the outer side, side s - 1); corner[e] = 1 unless it went straight.
+ * vec_min_rounds: init != 0: m_a = e, nxt_a = succ.  Then `rounds` Jacobi doubling rounds m'[e] = min(m[e], m[nxt[e]]),
+ *   nxt'[e] = nxt[nxt[e]]: round r reads set a (r even) or b (r odd), writes the other, and sets changed[r] = 1 if any m fell.  A round
+ *   that changed nothing has every m at its cycle's minimum; ceil(log2 E) rounds always reach that.
+ * vec_swap: at every interior vertex whose diagonal pixels share a label that the other two do not have: if the two edges of that label
+ *   that END there have one `ring` value, their successors are exchanged.
+ * vec_rank_init / vec_rank_rounds: every cycle cut at its leader (ring[e] == e): steps / area = edges, and twice the signed area, from e
+ *   up to the leader, by the same doubling and the same changed words; mark[e] = 1 at leaders.
+ * vec_ring_info: per ring r = ridx[leader]: its label, edge count and signed area.
+ * vec_place: pos[e] = ring_base[r] + rank of e in its ring (leader = 0), corner_ord[pos[e]] = corner[e].
+ * vec_emit: xy[voff[pos[e]]] = the end vertex (x, y) of every corner edge e.
+ * No atomic decides a position.  Bad arguments return -1 before any launch. */
+int unet_vec_flags(const uint8_t* mask, const int32_t* labels, int H, int W, const uint32_t* exclude8, uint8_t* flags, void* stream);
+long long unet_vec_scan_words(long long n);
+int unet_vec_scan(const uint8_t* in, long long n, int32_t* out, long long* blocks, void* stream);
+int unet_vec_read(const long long* dev, int count, long long* host, void* stream);
+int unet_vec_succ(const uint8_t* flags, const int32_t* offs, int H, int W, long long E, int32_t* succ, uint8_t* corner, void* stream);
+int unet_vec_min_rounds(const int32_t* succ, long long E, int32_t* m_a, int32_t* nxt_a, int32_t* m_b, int32_t* nxt_b, int init, int rounds,
+                        int32_t* changed, void* stream);
+int unet_vec_swap(const int32_t* labels, const uint8_t* flags, const int32_t* offs, int H, int W, const int32_t* ring, int32_t* succ,
+                  void* stream);
+int unet_vec_rank_init(const uint8_t* flags, const int32_t* offs, int H, int W, const int32_t* succ, const int32_t* ring, int32_t* steps,
+                       int32_t* nxt, long long* area, uint8_t* mark, long long E, void* stream);
+int unet_vec_rank_rounds(long long E, int32_t* steps_a, int32_t* nxt_a, long long* area_a, int32_t* steps_b, int32_t* nxt_b, long long* area_b,
+                         int rounds, int32_t* changed, void* stream);
+int unet_vec_ring_info(const uint8_t* flags, const int32_t* offs, const int32_t* labels, int H, int W, const int32_t* succ, const int32_t* ring,
+                       const int32_t* ridx, const int32_t* steps, const long long* area, long long R, int32_t* ring_label, long long* ring_len,
+                       long long* ring_area, void* stream);
+int unet_vec_place(const int32_t* ring, const int32_t* steps, const int32_t* ridx, const long long* ring_base, const long long* ring_len,
+                   const uint8_t* corner, long long E, long long R, int32_t* pos, uint8_t* corner_ord, void* stream);
+int unet_vec_emit(const uint8_t* flags, const int32_t* offs, int H, int W, const uint8_t* corner, const int32_t* pos, const int32_t* voff,
+                  long long E, long long V, int32_t* xy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

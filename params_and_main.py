@@ -89,11 +89,16 @@ COMPRESS = None
 # image, i.e. a cloud-optimised GeoTIFF -- "auto" takes "mode" for class masks and "average" for everything else
 TILE = None
 OVERVIEWS = None
+# polygons of the merged class mask (merge = True, class output), traced on the GPU and written as <merged raster stem>.geojson: VECTOR
+# False | True; VECTOR_EXCLUDE None | a class id | a list of class ids that get no polygon (with class_zero, NO_Data never gets one)
+VECTOR = False
+VECTOR_EXCLUDE = None
 
 
 def main():
     global large_file, specific_class, all_classes, transforms, VALID_SCENES, self_attention, monitor, loss_func, LR_FINDER
     global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS
+    global VECTOR, VECTOR_EXCLUDE
     t0 = time.time()
     if enable_extra_parameters:          # params_and_main.py:129-145
         import warnings
@@ -104,6 +109,7 @@ def main():
         all_classes, specific_class, enable_regression, large_file, max_empty = False, None, False, False, 0.9
         ARCHITECTURE, self_attention = xresnet34, False
         TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS = None, "mean", None, None, None, None
+        VECTOR, VECTOR_EXCLUDE = False, None
     if Create_tiles:
         from create_tiles_unet import split_raster
         split_raster(path_to_raster=image_path, path_to_mask=mask_path, base_dir=base_dir, patch_size=patch_size,
@@ -124,6 +130,8 @@ def main():
             extra["tile"] = TILE
         if OVERVIEWS is not None:
             extra["overviews"] = OVERVIEWS
+        if VECTOR:
+            extra["vector"], extra["vector_exclude"] = True, VECTOR_EXCLUDE
         save_predictions(predict_model, predict_path, regression, merge, all_classes, specific_class, large_file, AOI, year,
                          validation_vision, class_zero, tta=TTA, **extra)
     print(f"Operation completed in {(time.time() - t0) / 60:.2f} minutes.")

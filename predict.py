@@ -38,6 +38,11 @@ without leaving the device.  Only for the class mask of a merged prediction (Val
 And ``compress=`` (None | "lzw") with ``predictor=`` (1 | 2): LZW-compressed GeoTIFF outputs.  A merged prediction is encoded where the merge
 assembled it -- on the device with one rank or RCCL (``unet_amd/tiffenc.py``), so only the compressed bytes reach the host -- and by the host
 encoder of ``unet_amd/tiffio.py`` otherwise (the int8 ``large_file`` merge, gloo ranks, per-tile outputs); the file is the same either way.
+
+And ``vector_path=`` (``predict_raster``) / ``vector=True`` (``save_predictions``) with ``vector_exclude=``: the polygons of the merged class mask
+as a GeoJSON file (``unet_amd/vectorize.py``), traced on the device of the rank that assembled the mask, after ``postprocess``; with one rank the
+mask never leaves the device for it, gloo ranks upload the assembled host mask.  Only for the class mask of a merged prediction and not with
+``large_file`` (ValueError otherwise, before the model is loaded).
 """
 from __future__ import annotations
 
@@ -60,6 +65,7 @@ from unet_amd.postprocess import check_postprocess
 from unet_amd.mosaic import MergePlan, blend_profile, check_blend, keep_windows, merge_order, sliding_windows
 from unet_amd.tiffio import check_compress, check_tiling, read_tiff, resolve_overviews, tiff_info, write_tiff
 from unet_amd.tta import parse as tta_codes
+from unet_amd.vectorize import check_vector, epsg_of_tags, vectorize_mask
 
 
 def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_zero=False, compress=None, predictor=1,
@@ -386,7 +392,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                    regression: bool = False, all_classes: bool = False, specific_class: Optional[int] = None, large_file: bool = False,
                    batch_size: int = 16, out_path=None, class_zero: bool = False, timing: Optional[dict] = None,
                    batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
-                   return_array: bool = True, tile=None, overviews=None):
+                   return_array: bool = True, tile=None, overviews=None, vector_path=None, vector_exclude=None):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -421,6 +427,12 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
              class mask, "average" for float probabilities, regression and the int8 large_file planes; "mode" on float outputs is refused.
              The pyramid is built and encoded on the device wherever the merged array is encoded there
     return_array  False (needs out_path): nothing is returned, and with compress="lzw" the merged array never goes to the host
+    vector_path  None | path of a GeoJSON file: the class mask (after postprocess) is polygonized on the device of the rank that assembled it
+             (unet_amd/vectorize.py: 4-connected components, one Polygon feature each, map coordinates of the output raster, the "crs"
+             member from the raster's GeoKeyDirectory); only for the class mask and not with large_file (ValueError).  Under class_zero
+             the NO_Data class 0 gets no polygon and the other ids are shifted as in the raster.  timing gains vector_seconds,
+             vector_polygons and vector_vertices
+    vector_exclude  None | int | iterable of class ids (the model's, before the class_zero shift) whose components get no polygon
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
@@ -428,7 +440,8 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     post = check_postprocess(postprocess, regression, all_classes, specific_class)
     check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
     tile, overviews = _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file)
-    if not return_array and out_path is None:
+    vec = check_vector(vector_path, vector_exclude, regression, all_classes, specific_class, large_file, True, class_zero)
+    if not return_array and out_path is None and vec is None:
         raise ValueError("return_array=False needs out_path: the prediction would go nowhere")
     model = getattr(model, "model", model)
     codes = tta_codes(tta, [(size, size)])
@@ -472,9 +485,13 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     keep_out = compress is not None and out_path is not None          # the encoder takes the array where the merge assembled it
     with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
         out = _run_merge(model, places, MH, MW, regression, bool(large_file and not regression), rank, world, batch_size, make_input, want, timing,
-                         codes, blend, post, keep_out)
+                         codes, blend, post, keep_out or vec is not None)
+    ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
+    if rank == 0 and vec is not None:
+        vectorize_mask(out, vector_path, vec, ogt, epsg_of_tags(tags), None, class_zero, timing)
+        if not keep_out and isinstance(out, torch.Tensor):
+            out = out.cpu().numpy()
     if rank == 0 and out_path is not None:
-        ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
         store_tif(out_path, out, ogt, tags, -9999 if regression else None, class_zero, compress, predictor, timing, tile, overviews)
     if timing is not None:
         timing.update(kept_windows=len(wins), all_windows=int(len(keep)), mosaic=(MH, MW))
@@ -634,7 +651,7 @@ def _tile_windows(batch_size: int, device, div255_twice: bool) -> Callable:
 def save_predictions(predict_model, predict_path, regression, merge=False, all_classes=False, specific_class=None, large_file=False,
                      AOI=None, year=None, validation_vision=True, class_zero=False, batch_size=16, timing: Optional[dict] = None,
                      batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
-                     tile=None, overviews=None):
+                     tile=None, overviews=None, vector: bool = False, vector_exclude=None):
     """tta: None | "flips" | "d4" | a tuple of D4 codes (see predict_raster and unet_amd/tta.py), merged and per-tile outputs alike.
     blend: "mean" | "gaussian" (see predict_raster): how the windows of a merged prediction combine; only with merge=True (per-tile
     outputs have no overlap) and not with large_file (ValueError before the model is loaded).
@@ -644,11 +661,14 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     device with one rank or RCCL); per-tile outputs (merge=False) use the host encoder.
     tile / overviews (see predict_raster): tiles and the overview pyramid of the MERGED raster only; per-tile outputs (merge=False) ignore
     them, as a tile is one block anyway.
+    vector / vector_exclude (see predict_raster's vector_path): True writes <merged raster stem>.geojson beside the merged raster, with the
+    class names of the model's vocab; only with merge=True, for the class mask and not with large_file (ValueError before the model is loaded).
     validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
     check_blend(blend, large_file, merge)
     post = check_postprocess(postprocess, regression, all_classes, specific_class, merge)
     check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
     tile, overviews = _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file)
+    vec = check_vector(vector or None, vector_exclude, regression, all_classes, specific_class, large_file, merge, class_zero)
     rank, local_rank, world = _dist_ctx()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model
@@ -667,7 +687,7 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     if merge:
         out, gt = _save_merged(model, tiles, geos, windows, rank, world, regression, _want(regression, all_classes, specific_class),
                                bool(large_file and not regression), batch_size, batch_invariant, codes, blend, timing, post,
-                               compress is not None)
+                               compress is not None or vec is not None)
     else:
         _save_tiles(model, tiles, geos, windows, rank, world, output_folder, regression, all_classes, specific_class, large_file, class_zero,
                     batch_size, batch_invariant, codes, compress, predictor)
@@ -682,6 +702,12 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     if rank != 0:
         return None
     name = "_".join(filter(None, [AOI, year, model_name, "prediction"])) + ".tif"
+    if vec is not None:
+        vocab = getattr(learn.dls, "vocab", None)
+        names = list(vocab) if vocab is not None and len(vocab) >= model.n_out else None
+        vectorize_mask(out, (output_folder / name).with_suffix(".geojson"), vec, gt, epsg_of_tags(geos[0][1]), names, class_zero, timing)
+        if compress is None and isinstance(out, torch.Tensor):
+            out = out.cpu().numpy()
     store_tif(output_folder / name, out, gt, geos[0][1], -9999 if regression else None, class_zero, compress, predictor, timing, tile, overviews)
     print(f"Prediction stored in {output_folder}.")
     return output_folder if regression else output_folder / name

@@ -256,6 +256,18 @@ _sig = {
     "unet_edt_workspace": (sz, [i, i, i]),
     "unet_border_edt": (i, [vp, i, i, i, i, i, vp, vp, vp]),
     "unet_border_weight": (i, [vp, vp, vp, i, f, C.c_double, ll, vp, vp]),
+    "unet_vec_flags": (i, [vp, vp, i, i, C.POINTER(C.c_uint32), vp, vp]),
+    "unet_vec_scan_words": (ll, [ll]),
+    "unet_vec_scan": (i, [vp, ll, vp, vp, vp]),
+    "unet_vec_read": (i, [vp, i, C.POINTER(C.c_longlong), vp]),
+    "unet_vec_succ": (i, [vp, vp, i, i, ll, vp, vp, vp]),
+    "unet_vec_min_rounds": (i, [vp, ll, vp, vp, vp, vp, i, i, vp, vp]),
+    "unet_vec_swap": (i, [vp, vp, vp, i, i, vp, vp, vp]),
+    "unet_vec_rank_init": (i, [vp, vp, i, i, vp, vp, vp, vp, vp, vp, ll, vp]),
+    "unet_vec_rank_rounds": (i, [ll, vp, vp, vp, vp, vp, vp, i, vp, vp]),
+    "unet_vec_ring_info": (i, [vp, vp, vp, i, i, vp, vp, vp, vp, vp, ll, vp, vp, vp, vp]),
+    "unet_vec_place": (i, [vp, vp, vp, vp, vp, vp, ll, ll, vp, vp, vp]),
+    "unet_vec_emit": (i, [vp, vp, i, i, vp, vp, vp, ll, ll, vp, vp]),
 }
 # bf16-storage twins: same argument lists (every tensor is a void pointer on this side)
 for _n in ("bn_stats", "affine_act", "bn_bwd_reduce", "bn_bwd_apply", "maxpool3x3s2", "maxpool3x3s2_bwd", "avgpool2_ceil",

@@ -1446,6 +1446,177 @@ def postprocess_counters(counters: torch.Tensor):
     return int(host[0]), int(host[1])
 
 
+# ---------------------------------------------------------------------------------------------- polygon rings (csrc/vectorize.hip)
+
+VEC_MAX_COUNT = 2 ** 31 - 1
+
+
+def _vec_count(what: str, name: str, v) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= VEC_MAX_COUNT:
+        raise ValueError(f"{what}: {name} must be an int in 1..2^31 - 1, got {v!r}")
+    return v
+
+
+def vec_exclude_words(exclude) -> list:
+    """class ids 0..255 (an iterable of ints) -> the 256-bit set as 8 words"""
+    words = [0] * 8
+    for c in exclude:
+        if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 255:
+            raise ValueError(f"exclude: class ids must be ints in 0..255, got {c!r}")
+        words[c >> 5] |= 1 << (c & 31)
+    return words
+
+
+def vec_flags(mask: torch.Tensor, labels: torch.Tensor, exclude, flags: torch.Tensor):
+    """flags [H, W] uint8: bit s = side s (N=0 W=1 S=2 E=3) of the pixel is a boundary edge; 0 for the classes in `exclude`"""
+    _pp_tensor("vec_flags", "mask", mask, torch.uint8, mask.shape)
+    _pp_tensor("vec_flags", "labels", labels, torch.int32, mask.shape)
+    _pp_tensor("vec_flags", "flags", flags, torch.uint8, mask.shape)
+    H, W = mask.shape
+    words = (C.c_uint32 * 8)(*vec_exclude_words(exclude))
+    check(lib.unet_vec_flags(mask.data_ptr(), labels.data_ptr(), H, W, words, flags.data_ptr(), _stream()), "vec_flags")
+
+
+def vec_scan_words(n: int) -> int:
+    """int64 words of the block-sum workspace of vec_scan over n bytes; the last one receives the total"""
+    return int(lib.unet_vec_scan_words(int(n)))
+
+
+def vec_scan(src: torch.Tensor, out: torch.Tensor, blocks: torch.Tensor):
+    """out (int32, src.numel()) = exclusive scan of popcount(src & 15) over the bytes of src; blocks[vec_scan_words - 1] = the total"""
+    n = src.numel() if isinstance(src, torch.Tensor) else 0
+    _vec_count("vec_scan", "the element count", n)
+    _pp_tensor("vec_scan", "src", src, torch.uint8)
+    _pp_tensor("vec_scan", "out", out, torch.int32, numel=n)
+    _pp_tensor("vec_scan", "blocks", blocks, torch.int64, numel=vec_scan_words(n))
+    check(lib.unet_vec_scan(src.data_ptr(), n, out.data_ptr(), blocks.data_ptr(), _stream()), "vec_scan")
+
+
+def vec_read(words: torch.Tensor, first: int = 0, count: int = 1) -> list:
+    """`count` int64 words of a device tensor from `first` on, as Python ints: one copy and one stream sync"""
+    _pp_tensor("vec_read", "words", words, torch.int64, numel=first + count)
+    if first < 0 or not 1 <= count <= 64:
+        raise ValueError(f"vec_read: first must be >= 0 and count in 1..64, got {first}, {count}")
+    host = (C.c_longlong * count)()
+    check(lib.unet_vec_read(words.data_ptr() + 8 * first, count, host, _stream()), "vec_read")
+    return [int(v) for v in host]
+
+
+def vec_succ(flags: torch.Tensor, offs: torch.Tensor, E: int, succ: torch.Tensor, corner: torch.Tensor):
+    """succ[e] (compact edge indices) and corner[e] = 1 where the walk turns after e"""
+    _pp_tensor("vec_succ", "flags", flags, torch.uint8, flags.shape)
+    _pp_tensor("vec_succ", "offs", offs, torch.int32, flags.shape)
+    _vec_count("vec_succ", "E", E)
+    _pp_tensor("vec_succ", "succ", succ, torch.int32, numel=E)
+    _pp_tensor("vec_succ", "corner", corner, torch.uint8, numel=E)
+    H, W = flags.shape
+    check(lib.unet_vec_succ(flags.data_ptr(), offs.data_ptr(), H, W, E, succ.data_ptr(), corner.data_ptr(), _stream()), "vec_succ")
+
+
+def vec_min_rounds(succ: torch.Tensor, E: int, a, b, init: bool, rounds: int, changed: torch.Tensor):
+    """`rounds` doubling rounds of the cycle minimum between the buffer sets a = (m, nxt) and b; the result is in b after an odd count"""
+    _vec_count("vec_min_rounds", "E", E)
+    _pp_tensor("vec_min_rounds", "succ", succ, torch.int32, numel=E)
+    for t in (*a, *b):
+        _pp_tensor("vec_min_rounds", "a / b", t, torch.int32, numel=E)
+    if isinstance(rounds, bool) or not isinstance(rounds, int) or not 0 <= rounds <= 64:
+        raise ValueError(f"vec_min_rounds: rounds must be an int in 0..64, got {rounds!r}")
+    _pp_tensor("vec_min_rounds", "changed", changed, torch.int32, numel=max(rounds, 1))
+    check(lib.unet_vec_min_rounds(succ.data_ptr(), E, a[0].data_ptr(), a[1].data_ptr(), b[0].data_ptr(), b[1].data_ptr(), int(bool(init)), rounds,
+                                  changed.data_ptr(), _stream()), "vec_min_rounds")
+
+
+def vec_swap(labels: torch.Tensor, flags: torch.Tensor, offs: torch.Tensor, ring: torch.Tensor, succ: torch.Tensor, E: int):
+    """exchanges the successors of the two edges that end in a saddle vertex when both lie in one ring"""
+    _pp_tensor("vec_swap", "labels", labels, torch.int32, labels.shape)
+    _pp_tensor("vec_swap", "flags", flags, torch.uint8, labels.shape)
+    _pp_tensor("vec_swap", "offs", offs, torch.int32, labels.shape)
+    _vec_count("vec_swap", "E", E)
+    _pp_tensor("vec_swap", "ring", ring, torch.int32, numel=E)
+    _pp_tensor("vec_swap", "succ", succ, torch.int32, numel=E)
+    H, W = labels.shape
+    check(lib.unet_vec_swap(labels.data_ptr(), flags.data_ptr(), offs.data_ptr(), H, W, ring.data_ptr(), succ.data_ptr(), _stream()), "vec_swap")
+
+
+def vec_rank_init(flags: torch.Tensor, offs: torch.Tensor, succ: torch.Tensor, ring: torch.Tensor, E: int, steps: torch.Tensor, nxt: torch.Tensor,
+                  area: torch.Tensor, mark: torch.Tensor):
+    """the lists of the ranking: every cycle cut at its leader; mark[e] = 1 at leaders"""
+    _pp_tensor("vec_rank_init", "flags", flags, torch.uint8, flags.shape)
+    _pp_tensor("vec_rank_init", "offs", offs, torch.int32, flags.shape)
+    _vec_count("vec_rank_init", "E", E)
+    for name, t in (("succ", succ), ("ring", ring), ("steps", steps), ("nxt", nxt)):
+        _pp_tensor("vec_rank_init", name, t, torch.int32, numel=E)
+    _pp_tensor("vec_rank_init", "area", area, torch.int64, numel=E)
+    _pp_tensor("vec_rank_init", "mark", mark, torch.uint8, numel=E)
+    H, W = flags.shape
+    check(lib.unet_vec_rank_init(flags.data_ptr(), offs.data_ptr(), H, W, succ.data_ptr(), ring.data_ptr(), steps.data_ptr(), nxt.data_ptr(),
+                                 area.data_ptr(), mark.data_ptr(), E, _stream()), "vec_rank_init")
+
+
+def vec_rank_rounds(E: int, a, b, rounds: int, changed: torch.Tensor):
+    """`rounds` doubling rounds of the list ranking between the buffer sets a = (steps, nxt, area) and b"""
+    _vec_count("vec_rank_rounds", "E", E)
+    for s in (a, b):
+        _pp_tensor("vec_rank_rounds", "steps", s[0], torch.int32, numel=E)
+        _pp_tensor("vec_rank_rounds", "nxt", s[1], torch.int32, numel=E)
+        _pp_tensor("vec_rank_rounds", "area", s[2], torch.int64, numel=E)
+    if isinstance(rounds, bool) or not isinstance(rounds, int) or not 0 <= rounds <= 64:
+        raise ValueError(f"vec_rank_rounds: rounds must be an int in 0..64, got {rounds!r}")
+    _pp_tensor("vec_rank_rounds", "changed", changed, torch.int32, numel=max(rounds, 1))
+    check(lib.unet_vec_rank_rounds(E, a[0].data_ptr(), a[1].data_ptr(), a[2].data_ptr(), b[0].data_ptr(), b[1].data_ptr(), b[2].data_ptr(), rounds,
+                                   changed.data_ptr(), _stream()), "vec_rank_rounds")
+
+
+def vec_ring_info(flags: torch.Tensor, offs: torch.Tensor, labels: torch.Tensor, succ: torch.Tensor, ring: torch.Tensor, ridx: torch.Tensor,
+                  steps: torch.Tensor, area: torch.Tensor, E: int, R: int, ring_label: torch.Tensor, ring_len: torch.Tensor, ring_area: torch.Tensor):
+    """per ring (index ridx[leader]): label, edge count, signed area"""
+    _pp_tensor("vec_ring_info", "flags", flags, torch.uint8, flags.shape)
+    _pp_tensor("vec_ring_info", "offs", offs, torch.int32, flags.shape)
+    _pp_tensor("vec_ring_info", "labels", labels, torch.int32, flags.shape)
+    _vec_count("vec_ring_info", "E", E)
+    _vec_count("vec_ring_info", "R", R)
+    for name, t in (("succ", succ), ("ring", ring), ("ridx", ridx), ("steps", steps)):
+        _pp_tensor("vec_ring_info", name, t, torch.int32, numel=E)
+    _pp_tensor("vec_ring_info", "area", area, torch.int64, numel=E)
+    _pp_tensor("vec_ring_info", "ring_label", ring_label, torch.int32, numel=R)
+    _pp_tensor("vec_ring_info", "ring_len", ring_len, torch.int64, numel=R)
+    _pp_tensor("vec_ring_info", "ring_area", ring_area, torch.int64, numel=R)
+    H, W = flags.shape
+    check(lib.unet_vec_ring_info(flags.data_ptr(), offs.data_ptr(), labels.data_ptr(), H, W, succ.data_ptr(), ring.data_ptr(), ridx.data_ptr(),
+                                 steps.data_ptr(), area.data_ptr(), R, ring_label.data_ptr(), ring_len.data_ptr(), ring_area.data_ptr(), _stream()),
+          "vec_ring_info")
+
+
+def vec_place(ring: torch.Tensor, steps: torch.Tensor, ridx: torch.Tensor, ring_base: torch.Tensor, ring_len: torch.Tensor, corner: torch.Tensor,
+              E: int, R: int, pos: torch.Tensor, corner_ord: torch.Tensor):
+    """pos[e] = the place of edge e in ring order; corner_ord = the corner marks in that order"""
+    _vec_count("vec_place", "E", E)
+    _vec_count("vec_place", "R", R)
+    for name, t in (("ring", ring), ("steps", steps), ("ridx", ridx), ("pos", pos)):
+        _pp_tensor("vec_place", name, t, torch.int32, numel=E)
+    _pp_tensor("vec_place", "ring_base", ring_base, torch.int64, numel=R)
+    _pp_tensor("vec_place", "ring_len", ring_len, torch.int64, numel=R)
+    _pp_tensor("vec_place", "corner", corner, torch.uint8, numel=E)
+    _pp_tensor("vec_place", "corner_ord", corner_ord, torch.uint8, numel=E)
+    check(lib.unet_vec_place(ring.data_ptr(), steps.data_ptr(), ridx.data_ptr(), ring_base.data_ptr(), ring_len.data_ptr(), corner.data_ptr(), E, R,
+                             pos.data_ptr(), corner_ord.data_ptr(), _stream()), "vec_place")
+
+
+def vec_emit(flags: torch.Tensor, offs: torch.Tensor, corner: torch.Tensor, pos: torch.Tensor, voff: torch.Tensor, E: int, V: int, xy: torch.Tensor):
+    """xy [V, 2] int32: the end vertex of every corner edge at its vertex index"""
+    _pp_tensor("vec_emit", "flags", flags, torch.uint8, flags.shape)
+    _pp_tensor("vec_emit", "offs", offs, torch.int32, flags.shape)
+    _vec_count("vec_emit", "E", E)
+    _vec_count("vec_emit", "V", V)
+    _pp_tensor("vec_emit", "corner", corner, torch.uint8, numel=E)
+    _pp_tensor("vec_emit", "pos", pos, torch.int32, numel=E)
+    _pp_tensor("vec_emit", "voff", voff, torch.int32, numel=E)
+    _pp_tensor("vec_emit", "xy", xy, torch.int32, numel=2 * V)
+    H, W = flags.shape
+    check(lib.unet_vec_emit(flags.data_ptr(), offs.data_ptr(), H, W, corner.data_ptr(), pos.data_ptr(), voff.data_ptr(), E, V, xy.data_ptr(), _stream()),
+          "vec_emit")
+
+
 # ---------------------------------------------------------------------------------------------- GeoTIFF strips on the device (csrc/tiff_encode.hip)
 
 def tiff_lzw_cap(n: int) -> int:

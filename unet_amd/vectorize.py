@@ -1,0 +1,346 @@
+"""Polygons of a merged uint8 class mask, traced on the device (csrc/vectorize.hip), and their GeoJSON file.
+tests/vectorize_ref.py restates every rule below in plain Python; the device arrays equal it bit for bit.
+
+polygonize(mask) labels the 4-connected components (label_components), traces the rings of every component and returns them as
+Polygons: only the corner vertices leave the device.  Connectivity 8 is out of scope: its components pinch at vertices and its holes
+would need a point-in-polygon assignment.
+
+Vertices    pixel corners (x, y), 0 <= x <= W, 0 <= y <= H, y down; pixel (y, x) covers [x, x + 1] x [y, y + 1].
+Edges       pixel p = y * W + x with label L has a boundary edge on side s (N=0 W=1 S=2 E=3) if the neighbour across that side is
+            outside the raster or has another label.  Dense edge id 4 p + s.  Edges are directed with the pixel on the LEFT of the walk as
+            seen on screen: N (x+1, y) -> (x, y), W (x, y) -> (x, y+1), S (x, y+1) -> (x+1, y+1), E (x+1, y+1) -> (x+1, y).  Exterior
+            rings run counter-clockwise on screen, and for a north-up geotransform counter-clockwise in map coordinates (RFC 7946).
+Successor   another boundary edge of the same label, the first that exists of: left (same pixel, side (s + 1) % 4), straight (the next
+            pixel along the walk, same side), right (the pixel diagonally ahead on the outer side, side (s - 1) % 4).
+Saddles     a saddle vertex is a 2 x 2 block whose diagonal pixels share a label while the other two differ from it.  Rings are the
+            cycles of the successor; after a first identification, at every saddle vertex whose two incoming edges of the diagonal pair
+            lie in the SAME ring their successors are swapped (in different rings they stay), and the rings are identified again.  Then no
+            ring visits a vertex twice, every component has exactly one ring of positive area whose smallest edge id is 4 * label, the
+            signed areas of its rings sum to its pixel count, and an even-odd fill of its rings is exactly its pixels.
+Rings       a ring's leader is its smallest edge id.  Its vertices are the END vertices of the edges whose successor has another side
+            code (corners only), in walk order from the first such edge at or after the leader; the closing point is not repeated.
+Area        1/2 sum(x[i+1] y[i] - x[i] y[i+1]) as int64: +1 for one pixel, negative for holes.
+Order       rings by ascending leader; polygons by ascending label; within a polygon the exterior ring, then the holes by leader.
+
+Passes: labels, side flags, a scan to compact edge indices, successors, cycle minimum by pointer doubling, saddle swaps, cycle minimum
+again, list ranking (with the area terms), ring info, placement in ring order, a scan of the corner marks, vertices.  Doubling runs at
+most ceil(log2 E) + 1 rounds, in groups after each of which one word says whether the last round still changed anything.  Host reads per
+call: E, R, V, P and those words.  Ring- and polygon-level bookkeeping (a sort and a few scans over R entries) uses torch.
+
+Memory: 10 bytes per pixel (labels 4, flags 1, edge offsets 4, the mask 1) and 42 bytes per edge (six int32 arrays, two int64 arrays of
+area terms, two byte arrays), beside 28 bytes per ring and 8 per vertex.  Every buffer that a kernel writes comes from _alloc."""
+from __future__ import annotations
+
+import json
+import os
+import time
+from dataclasses import dataclass, fields
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import ops
+from .postprocess import _is_int, _to_device
+
+_GROUP = 4                    # doubling rounds per host look at the convergence words
+
+
+def _alloc(shape, dtype, device) -> torch.Tensor:
+    """every device buffer that a kernel of this module writes (the tests put guard bands around them here)"""
+    return torch.empty(tuple(shape), dtype=dtype, device=device)
+
+
+@dataclass
+class Polygons:
+    """rings in ascending leader order, polygons in ascending label order (the module docstring has the rules)"""
+    xy: torch.Tensor                   # int32 [V, 2]
+    ring_start: torch.Tensor           # int64 [R + 1]
+    ring_label: torch.Tensor           # int32 [R]
+    ring_area: torch.Tensor            # int64 [R]
+    poly_label: torch.Tensor           # int32 [P]
+    poly_class: torch.Tensor           # uint8 [P]
+    poly_pixels: torch.Tensor          # int64 [P]
+    poly_ring_start: torch.Tensor      # int64 [P + 1]
+    poly_rings: torch.Tensor           # int64 [R]: ring indices, per polygon the exterior first, then the holes by leader
+    edges: int = 0                     # boundary edges traced
+
+    def cpu(self) -> "Polygons":
+        return Polygons(**{f.name: (getattr(self, f.name).cpu() if f.name != "edges" else self.edges) for f in fields(self)})
+
+    @property
+    def n_polygons(self) -> int:
+        return int(self.poly_label.shape[0])
+
+    @property
+    def n_rings(self) -> int:
+        return int(self.ring_label.shape[0])
+
+    @property
+    def n_vertices(self) -> int:
+        return int(self.xy.shape[0])
+
+
+def check_exclude(exclude) -> tuple:
+    """None | int | iterable of class ids 0..255 -> a sorted tuple"""
+    if exclude is None:
+        return ()
+    if _is_int(exclude):
+        exclude = (exclude,)
+    try:
+        ids = [c for c in exclude]
+    except TypeError:
+        raise ValueError(f"exclude must be None, an int or an iterable of class ids 0..255, got {exclude!r}") from None
+    for c in ids:
+        if not _is_int(c) or not 0 <= c <= 255:
+            raise ValueError(f"exclude: class ids must be ints in 0..255, got {c!r}")
+    return tuple(sorted({int(c) for c in ids}))
+
+
+def _empty(dev) -> Polygons:
+    z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)          # noqa: E731
+    return Polygons(z((0, 2), torch.int32), z((1,), torch.int64), z((0,), torch.int32), z((0,), torch.int64), z((0,), torch.int32),
+                    z((0,), torch.uint8), z((0,), torch.int64), z((1,), torch.int64), z((0,), torch.int64), 0)
+
+
+def _scan_total(src: torch.Tensor, out: torch.Tensor, blocks: torch.Tensor) -> int:
+    ops.vec_scan(src, out, blocks)
+    return ops.vec_read(blocks, ops.vec_scan_words(src.numel()) - 1, 1)[0]          # a host read
+
+
+def _max_rounds(E: int) -> int:
+    return (E - 1).bit_length() + 1          # ceil(log2 E) + 1
+
+
+def _settled(changed: torch.Tensor, g: int) -> bool:
+    """did the last of the g rounds change nothing?  (one host read; the words are int32 pairs)"""
+    words = ops.vec_read(changed, 0, (g + 1) // 2)
+    return not (words[(g - 1) // 2] >> (32 * ((g - 1) % 2))) & 0xFFFFFFFF
+
+
+def _doubling(E: int, run, a, b, changed: torch.Tensor):
+    """groups of doubling rounds a -> b -> a ... until one changes nothing or ceil(log2 E) + 1 are done; returns (newest set, other)"""
+    left = _max_rounds(E)
+    while left > 0:
+        g = min(_GROUP, left)
+        run(a, b, g)
+        left -= g
+        if g % 2:
+            a, b = b, a
+        if _settled(changed, g):
+            break
+    return a, b
+
+
+class _Stages:
+    """milliseconds per stage for scripts/vectorize_bench.py: a device synchronise at every mark, so only when a dict is passed in"""
+
+    def __init__(self, out: Optional[dict]):
+        self.out = out
+        if out is not None:
+            torch.cuda.synchronize()
+            self.t = time.perf_counter()
+
+    def mark(self, name: str):
+        if self.out is not None:
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            self.out[name] = self.out.get(name, 0.0) + (now - self.t) * 1e3
+            self.t = now
+
+
+def _polygonize(m: torch.Tensor, exclude: tuple, stages: Optional[dict] = None) -> Polygons:
+    st = _Stages(stages)
+    dev = m.device
+    H, W = m.shape
+    n = H * W
+    i32, i64, u8 = torch.int32, torch.int64, torch.uint8
+    labels, counters = _alloc((H, W), i32, dev), _alloc((4,), i32, dev)
+    ops.cc_label(m, 4, labels, counters)
+    ops.postprocess_counters(counters)
+    st.mark("label")
+    flags, offs = _alloc((H, W), u8, dev), _alloc((H, W), i32, dev)
+    ops.vec_flags(m, labels, exclude, flags)
+    E = _scan_total(flags, offs, _alloc((ops.vec_scan_words(n),), i64, dev))
+    st.mark("flags_scan")
+    if E > ops.VEC_MAX_COUNT:
+        raise ValueError(f"polygonize: {E} boundary edges exceed 2^31 - 1 (edge indices are int32)")
+    if E == 0:
+        return _empty(dev)
+    succ, corner = _alloc((E,), i32, dev), _alloc((E,), u8, dev)
+    ops.vec_succ(flags, offs, E, succ, corner)
+    st.mark("succ")
+    w = [_alloc((E,), i32, dev) for _ in range(5)]
+    changed = _alloc((32,), i64, dev)
+    ch32 = changed.view(i32)
+
+    def identify():
+        first = [True]
+
+        def run(a, b, g):
+            ops.vec_min_rounds(succ, E, a, b, first[0], g, ch32)
+            first[0] = False
+        return _doubling(E, run, (w[0], w[1]), (w[2], w[3]), changed)
+
+    (ring, _), _ = identify()
+    st.mark("rings_first")
+    ops.vec_swap(labels, flags, offs, ring, succ, E)
+    st.mark("swap")
+    (ring, free0), (free1, free2) = identify()
+    st.mark("rings_second")
+
+    mark = _alloc((E,), u8, dev)
+    area_a, area_b = _alloc((E,), i64, dev), _alloc((E,), i64, dev)
+    ops.vec_rank_init(flags, offs, succ, ring, E, free0, free1, area_a, mark)
+    (steps, free0, area), (free1, free2, _) = _doubling(E, lambda a, b, g: ops.vec_rank_rounds(E, a, b, g, ch32), (free0, free1, area_a),
+                                                        (free2, w[4], area_b), changed)
+    st.mark("rank")
+    blocks = _alloc((ops.vec_scan_words(E),), i64, dev)
+    ridx = free1
+    R = _scan_total(mark, ridx, blocks)
+    ring_label, ring_len, ring_area = _alloc((R,), i32, dev), _alloc((R,), i64, dev), _alloc((R,), i64, dev)
+    ops.vec_ring_info(flags, offs, labels, succ, ring, ridx, steps, area, E, R, ring_label, ring_len, ring_area)
+    ring_base = torch.cumsum(ring_len, 0) - ring_len
+    pos, corner_ord = free2, mark
+    ops.vec_place(ring, steps, ridx, ring_base, ring_len, corner, E, R, pos, corner_ord)
+    voff = free0
+    V = _scan_total(corner_ord, voff, blocks)
+    xy = _alloc((V, 2), i32, dev)
+    ops.vec_emit(flags, offs, corner, pos, voff, E, V, xy)
+    st.mark("place_emit")
+    ring_start = torch.cat([voff[ring_base].to(i64), torch.tensor([V], dtype=i64, device=dev)])
+
+    # polygon level: a sort of R keys (label, leader) -- rings are in leader order, so their index stands for the leader
+    order = torch.argsort(ring_label.to(i64) * R + torch.arange(R, dtype=i64, device=dev))
+    by_label = ring_label[order]
+    first = torch.ones(R, dtype=torch.bool, device=dev)
+    first[1:] = by_label[1:] != by_label[:-1]
+    starts = torch.nonzero(first).flatten()
+    poly_label = by_label[starts]
+    poly_ring_start = torch.cat([starts, torch.tensor([R], dtype=i64, device=dev)])
+    run = torch.cat([torch.zeros(1, dtype=i64, device=dev), torch.cumsum(ring_area[order], 0)])
+    st.mark("polygons")
+    return Polygons(xy, ring_start, ring_label, ring_area, poly_label, m.view(-1)[poly_label.to(i64)], run[poly_ring_start[1:]] - run[poly_ring_start[:-1]],
+                    poly_ring_start, order, E)
+
+
+def polygonize(mask, exclude=None, stages: Optional[dict] = None) -> Polygons:
+    """Polygons (device tensors) of the 4-connected components of a contiguous uint8 [H, W] class mask (device tensor, host tensor or NumPy
+    array; host input is uploaded).  exclude: None, an int or an iterable of class ids 0..255 whose components get no polygon.
+    Connectivity 8 is not offered: its components pinch at vertices and holes would need a point-in-polygon assignment.
+    stages: a dict that receives the milliseconds of every stage (this synchronises the device after each: for measurements only)."""
+    exclude = check_exclude(exclude)
+    m, _ = _to_device(mask, torch.uint8, "polygonize")
+    return _polygonize(m, exclude, stages)
+
+
+# ------------------------------------------------------------------------------------------------------------------ GeoJSON (host)
+
+_ARRAYS = ("xy", "ring_start", "poly_label", "poly_class", "poly_pixels", "poly_ring_start", "poly_rings")
+
+
+def _host_arrays(polys) -> dict:
+    """Polygons (device or host) or a mapping of arrays -> NumPy arrays"""
+    out = {}
+    for k in _ARRAYS:
+        v = polys[k] if isinstance(polys, dict) else getattr(polys, k)
+        out[k] = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    return out
+
+
+def epsg_of_tags(tags) -> Optional[int]:
+    """the EPSG code in the GeoKeyDirectory (tag 34735) of read_tiff's meta["tags"]: key 3072 (projected), else 2048 (geographic); 32767
+    (user-defined) and values stored in another tag count as unknown"""
+    if not tags or 34735 not in tags:
+        return None
+    d = [int(v) for v in tags[34735]]
+    keys = {}
+    for i in range(d[3] if len(d) >= 4 else 0):
+        entry = d[4 + 4 * i:8 + 4 * i]
+        if len(entry) == 4 and entry[1] == 0 and entry[2] == 1:          # the value sits in the entry itself
+            keys[entry[0]] = entry[3]
+    for k in (3072, 2048):
+        if k in keys and keys[k] not in (0, 32767):
+            return keys[k]
+    return None
+
+
+def check_geojson_args(geotransform=None, epsg=None):
+    if geotransform is not None:
+        gt = tuple(float(v) for v in geotransform)
+        if len(gt) != 6 or gt[1] == 0 or gt[5] == 0:
+            raise ValueError(f"geotransform must be six numbers with non-zero pixel sizes, got {geotransform!r}")
+        if gt[2] != 0 or gt[4] != 0:
+            raise ValueError("geotransform with rotation terms is not supported")
+    if epsg is not None and (not _is_int(epsg) or epsg <= 0):
+        raise ValueError(f"epsg must be None or a positive int, got {epsg!r}")
+
+
+def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, codes=None, class_zero: bool = False) -> int:
+    """One FeatureCollection with one Polygon feature per component, in poly_label order: the exterior ring, then the holes, each closed by
+    repeating its first point.  Coordinates are X = gt[0] + x gt[1], Y = gt[3] + y gt[5] in float64, written with repr; integer pixel
+    coordinates without a geotransform.  Properties: class (the id as the raster on disk holds it: class - 1 under class_zero, where
+    class 0 -- NO_Data -- gets no feature), name (codes[class], if codes are given), pixels, area (pixels |gt[1] gt[5]|).  With an EPSG code
+    the legacy "crs" member names urn:ogc:def:crs:EPSG::<code>.  Returns the number of features.  Host code."""
+    check_geojson_args(geotransform, epsg)
+    a = _host_arrays(polys)
+    gt = None if geotransform is None else tuple(float(v) for v in geotransform)
+    xy = a["xy"].astype(np.int64)
+    if gt is None:
+        pts = [f"[{x},{y}]" for x, y in xy.tolist()]
+    else:
+        X, Y = gt[0] + xy[:, 0].astype(np.float64) * gt[1], gt[3] + xy[:, 1].astype(np.float64) * gt[5]
+        pts = [f"[{x!r},{y!r}]" for x, y in zip(X.tolist(), Y.tolist())]
+    if codes is not None and a["poly_class"].size and int(a["poly_class"].max()) >= len(codes):
+        raise ValueError(f"codes names {len(codes)} classes, the polygons hold class {int(a['poly_class'].max())}")
+    rs, prs, rings = a["ring_start"].tolist(), a["poly_ring_start"].tolist(), a["poly_rings"].tolist()
+    px_area = 1.0 if gt is None else abs(gt[1] * gt[5])
+    feats = []
+    for i, (cls, pixels) in enumerate(zip(a["poly_class"].tolist(), a["poly_pixels"].tolist())):
+        if class_zero and cls == 0:
+            continue
+        props = {"class": cls - 1 if class_zero else cls}
+        if codes is not None:
+            props["name"] = str(codes[cls])
+        props["pixels"] = pixels
+        props["area"] = pixels * px_area
+        coords = ",".join("[" + ",".join(pts[rs[r]:rs[r + 1]] + pts[rs[r]:rs[r] + 1]) + "]" for r in rings[prs[i]:prs[i + 1]])
+        feats.append('{"type":"Feature","properties":' + json.dumps(props) + ',"geometry":{"type":"Polygon","coordinates":[' + coords + "]}}")
+    head = '{"type":"FeatureCollection",'
+    if epsg is not None:
+        head += '"crs":{"type":"name","properties":{"name":"urn:ogc:def:crs:EPSG::%d"}},' % int(epsg)
+    with open(os.fspath(path), "w") as f:
+        f.write(head + '"features":[\n' + ",\n".join(feats) + "\n]}\n")
+    return len(feats)
+
+
+# ------------------------------------------------------------------------------------------------------------------ entry points
+
+def check_vector(vector, vector_exclude=None, regression: bool = False, all_classes: bool = False, specific_class=None, large_file: bool = False,
+                 merge: bool = True, class_zero: bool = False) -> Optional[tuple]:
+    """the vector_path= / vector= and vector_exclude= arguments of predict_raster / save_predictions, validated before the model is loaded or
+    anything touches the GPU -> the classes to exclude (a tuple), or None when no vector file is wanted"""
+    if vector is None or vector is False:
+        if vector_exclude is not None:
+            raise ValueError("vector_exclude without a vector output")
+        return None
+    exclude = check_exclude(vector_exclude)
+    if regression or all_classes or specific_class is not None:
+        raise ValueError("a vector output needs the class mask: not with regression, all_classes or specific_class")
+    if large_file:
+        raise ValueError("a vector output needs the class mask on one device: not with large_file")
+    if not merge:
+        raise ValueError("a vector output needs merge=True: per-tile outputs are not polygonized")
+    if class_zero:
+        exclude = tuple(sorted(set(exclude) | {0}))
+    return exclude
+
+
+def vectorize_mask(mask, path, exclude=(), geotransform=None, epsg=None, codes=None, class_zero: bool = False, timing: Optional[dict] = None) -> Polygons:
+    """polygonize + write_geojson of an assembled class mask (device or host); timing gains vector_seconds / _polygons / _vertices"""
+    t0 = time.perf_counter()
+    polys = polygonize(mask, exclude)
+    n = write_geojson(path, polys, geotransform, epsg, codes, class_zero)
+    if timing is not None:
+        timing.update(vector_seconds=time.perf_counter() - t0, vector_polygons=n, vector_vertices=polys.n_vertices)
+    return polys
