@@ -787,6 +787,42 @@ int unet_vec_place(const int32_t* ring, const int32_t* steps, const int32_t* rid
 int unet_vec_emit(const uint8_t* flags, const int32_t* offs, int H, int W, const uint8_t* corner, const int32_t* pos, const int32_t* voff,
                   long long E, long long V, int32_t* xy, void* stream);
 
+/* ---------------------------------------------------- ring simplification --
+ * Arc-based Douglas-Peucker on the traced rings (csrc/simplify.hip, unet_amd/vectorize.py).  C candidates (corners and the
+ * nodes a ring passes) lie in ring order: vec_place / vec_scan / vec_emit run on the marks of simp_marks give their coordinates cxy.
+ * simp_marks: cand[e] bit 0 = the end vertex of edge e is a candidate, bit 4 = it is a node (at least 3 of its 4 unit segments are
+ *   borders between labels, outside the raster being one label, or it is a raster corner).
+ * simp_gather: cring[k] = ring index, cnode[k] = node mark of candidate k = coff[pos[e]].
+ * simp_closed: per ring the node count and the anchor (its first node by (y, x), else its candidate with the smallest (y, x)); for rings
+ *   with fewer than 2 nodes the candidate farthest from the anchor (squared distance, ties to the smallest (y, x)).  Then keep[k] = node,
+ *   anchor or far point, and lo / hi = k for kept candidates, else the cyclic neighbours within the ring (cs = first candidate, cn =
+ *   candidate count per ring).  nnodes, akey, fard, fark are R-entry work arrays.
+ * simp_near_rounds: Jacobi doubling lo' = lo[lo], hi' = hi[hi] between two buffer sets, changed[r] as in vec_min_rounds; settles at the
+ *   nearest kept candidate before / after.
+ * simp_dp_rounds: `rounds` rounds.  Each: every live candidate takes |c|, c = (Q - P) x (Z - P) against its segment lo .. hi; the segment's
+ *   maximum of (|c|, smallest (y, x)) is kept iff 256 c^2 > q^2 |Q - P|^2 (128-bit, q in sixteenths of a pixel, 0..65536); its segment
+ *   splits there, or its whole interior is dropped.  first != 0 on the first call.  changed[r] = 1 if round r still had a live segment.
+ *   key, slot (C words each) and win (C) are work arrays.
+ * simp_emit: xy[vbase[r] + koff[k] - kstart[r]] = cxy[k], vring = newring[r], for kept candidates of rings with newring[r] >= 0.
+ * simp_area: area2[r] = sum of x1 y0 - x0 y1 over the ring's consecutive vertices (twice the signed area).
+ * Atomics take minima, maxima and exact integer sums only.  Bad arguments return -1 before any launch. */
+int unet_simp_marks(const int32_t* labels, const uint8_t* flags, const int32_t* offs, const uint8_t* corner, int H, int W, long long E,
+                    uint8_t* cand, void* stream);
+int unet_simp_gather(const int32_t* ring, const int32_t* ridx, const int32_t* pos, const int32_t* coff, const uint8_t* cand, long long E,
+                     long long R, long long C, int32_t* cring, uint8_t* cnode, void* stream);
+int unet_simp_closed(const int32_t* cxy, const int32_t* cring, const uint8_t* cnode, const int32_t* cs, const int32_t* cn, long long C,
+                     long long R, int W, int32_t* nnodes, unsigned long long* akey, unsigned long long* fard, unsigned long long* fark,
+                     uint8_t* keep, int32_t* lo, int32_t* hi, void* stream);
+int unet_simp_near_rounds(long long C, int32_t* lo_a, int32_t* hi_a, int32_t* lo_b, int32_t* hi_b, int rounds, int32_t* changed, void* stream);
+int unet_simp_dp_rounds(const int32_t* cxy, const int32_t* cring, const int32_t* cn, long long C, long long R, int W, int q, int first, int rounds,
+                        uint8_t* keep, int32_t* lo, int32_t* hi, unsigned long long* key, unsigned long long* slot, int32_t* win,
+                        int32_t* changed, void* stream);
+int unet_simp_emit(const int32_t* cxy, const int32_t* cring, const uint8_t* keep, const int32_t* koff, const int32_t* kstart,
+                   const long long* vbase, const int32_t* newring, long long C, long long R, long long V, int32_t* xy, int32_t* vring,
+                   void* stream);
+int unet_simp_area(const int32_t* xy, const int32_t* vring, const long long* ring_start, long long V, long long R, long long* area2,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

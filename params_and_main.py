@@ -93,12 +93,15 @@ OVERVIEWS = None
 # False | True; VECTOR_EXCLUDE None | a class id | a list of class ids that get no polygon (with class_zero, NO_Data never gets one)
 VECTOR = False
 VECTOR_EXCLUDE = None
+# VECTOR_SIMPLIFY None | a tolerance in pixels (0..4096): the rings are simplified on the GPU (Douglas-Peucker per shared border, so that
+# neighbouring polygons keep one common border) before they are written
+VECTOR_SIMPLIFY = None
 
 
 def main():
     global large_file, specific_class, all_classes, transforms, VALID_SCENES, self_attention, monitor, loss_func, LR_FINDER
     global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS
-    global VECTOR, VECTOR_EXCLUDE
+    global VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY
     t0 = time.time()
     if enable_extra_parameters:          # params_and_main.py:129-145
         import warnings
@@ -109,7 +112,7 @@ def main():
         all_classes, specific_class, enable_regression, large_file, max_empty = False, None, False, False, 0.9
         ARCHITECTURE, self_attention = xresnet34, False
         TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS = None, "mean", None, None, None, None
-        VECTOR, VECTOR_EXCLUDE = False, None
+        VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY = False, None, None
     if Create_tiles:
         from create_tiles_unet import split_raster
         split_raster(path_to_raster=image_path, path_to_mask=mask_path, base_dir=base_dir, patch_size=patch_size,
@@ -132,6 +135,8 @@ def main():
             extra["overviews"] = OVERVIEWS
         if VECTOR:
             extra["vector"], extra["vector_exclude"] = True, VECTOR_EXCLUDE
+            if VECTOR_SIMPLIFY is not None:
+                extra["vector_simplify"] = VECTOR_SIMPLIFY
         save_predictions(predict_model, predict_path, regression, merge, all_classes, specific_class, large_file, AOI, year,
                          validation_vision, class_zero, tta=TTA, **extra)
     print(f"Operation completed in {(time.time() - t0) / 60:.2f} minutes.")

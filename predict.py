@@ -42,7 +42,8 @@ encoder of ``unet_amd/tiffio.py`` otherwise (the int8 ``large_file`` merge, gloo
 And ``vector_path=`` (``predict_raster``) / ``vector=True`` (``save_predictions``) with ``vector_exclude=``: the polygons of the merged class mask
 as a GeoJSON file (``unet_amd/vectorize.py``), traced on the device of the rank that assembled the mask, after ``postprocess``; with one rank the
 mask never leaves the device for it, gloo ranks upload the assembled host mask.  Only for the class mask of a merged prediction and not with
-``large_file`` (ValueError otherwise, before the model is loaded).
+``large_file`` (ValueError otherwise, before the model is loaded).  ``vector_simplify=`` (a tolerance in pixels) simplifies the rings on
+the device before they are written, every shared border once and identically from both sides.
 """
 from __future__ import annotations
 
@@ -392,7 +393,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                    regression: bool = False, all_classes: bool = False, specific_class: Optional[int] = None, large_file: bool = False,
                    batch_size: int = 16, out_path=None, class_zero: bool = False, timing: Optional[dict] = None,
                    batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
-                   return_array: bool = True, tile=None, overviews=None, vector_path=None, vector_exclude=None):
+                   return_array: bool = True, tile=None, overviews=None, vector_path=None, vector_exclude=None, vector_simplify=None):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -433,6 +434,9 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
              the NO_Data class 0 gets no polygon and the other ids are shifted as in the raster.  timing gains vector_seconds,
              vector_polygons and vector_vertices
     vector_exclude  None | int | iterable of class ids (the model's, before the class_zero shift) whose components get no polygon
+    vector_simplify  None | a tolerance in pixels, 0..4096 (needs vector_path): the rings are simplified on the device before they are written,
+             by a Douglas-Peucker on the arcs between the junctions of the borders, so that neighbouring polygons keep one common border
+             (unet_amd/vectorize.py); polygons that shrink to fewer than 3 vertices get no feature.  timing gains vector_vertices_raw
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
@@ -440,7 +444,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     post = check_postprocess(postprocess, regression, all_classes, specific_class)
     check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
     tile, overviews = _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file)
-    vec = check_vector(vector_path, vector_exclude, regression, all_classes, specific_class, large_file, True, class_zero)
+    vec = check_vector(vector_path, vector_exclude, regression, all_classes, specific_class, large_file, True, class_zero, vector_simplify)
     if not return_array and out_path is None and vec is None:
         raise ValueError("return_array=False needs out_path: the prediction would go nowhere")
     model = getattr(model, "model", model)
@@ -488,7 +492,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                          codes, blend, post, keep_out or vec is not None)
     ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
     if rank == 0 and vec is not None:
-        vectorize_mask(out, vector_path, vec, ogt, epsg_of_tags(tags), None, class_zero, timing)
+        vectorize_mask(out, vector_path, vec, ogt, epsg_of_tags(tags), None, class_zero, timing, vector_simplify)
         if not keep_out and isinstance(out, torch.Tensor):
             out = out.cpu().numpy()
     if rank == 0 and out_path is not None:
@@ -651,7 +655,7 @@ def _tile_windows(batch_size: int, device, div255_twice: bool) -> Callable:
 def save_predictions(predict_model, predict_path, regression, merge=False, all_classes=False, specific_class=None, large_file=False,
                      AOI=None, year=None, validation_vision=True, class_zero=False, batch_size=16, timing: Optional[dict] = None,
                      batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
-                     tile=None, overviews=None, vector: bool = False, vector_exclude=None):
+                     tile=None, overviews=None, vector: bool = False, vector_exclude=None, vector_simplify=None):
     """tta: None | "flips" | "d4" | a tuple of D4 codes (see predict_raster and unet_amd/tta.py), merged and per-tile outputs alike.
     blend: "mean" | "gaussian" (see predict_raster): how the windows of a merged prediction combine; only with merge=True (per-tile
     outputs have no overlap) and not with large_file (ValueError before the model is loaded).
@@ -663,12 +667,13 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     them, as a tile is one block anyway.
     vector / vector_exclude (see predict_raster's vector_path): True writes <merged raster stem>.geojson beside the merged raster, with the
     class names of the model's vocab; only with merge=True, for the class mask and not with large_file (ValueError before the model is loaded).
+    vector_simplify: None | a tolerance in pixels (see predict_raster); needs vector=True.
     validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
     check_blend(blend, large_file, merge)
     post = check_postprocess(postprocess, regression, all_classes, specific_class, merge)
     check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
     tile, overviews = _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file)
-    vec = check_vector(vector or None, vector_exclude, regression, all_classes, specific_class, large_file, merge, class_zero)
+    vec = check_vector(vector or None, vector_exclude, regression, all_classes, specific_class, large_file, merge, class_zero, vector_simplify)
     rank, local_rank, world = _dist_ctx()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model
@@ -705,7 +710,7 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     if vec is not None:
         vocab = getattr(learn.dls, "vocab", None)
         names = list(vocab) if vocab is not None and len(vocab) >= model.n_out else None
-        vectorize_mask(out, (output_folder / name).with_suffix(".geojson"), vec, gt, epsg_of_tags(geos[0][1]), names, class_zero, timing)
+        vectorize_mask(out, (output_folder / name).with_suffix(".geojson"), vec, gt, epsg_of_tags(geos[0][1]), names, class_zero, timing, vector_simplify)
         if compress is None and isinstance(out, torch.Tensor):
             out = out.cpu().numpy()
     store_tif(output_folder / name, out, gt, geos[0][1], -9999 if regression else None, class_zero, compress, predictor, timing, tile, overviews)

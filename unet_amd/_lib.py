@@ -268,6 +268,13 @@ _sig = {
     "unet_vec_ring_info": (i, [vp, vp, vp, i, i, vp, vp, vp, vp, vp, ll, vp, vp, vp, vp]),
     "unet_vec_place": (i, [vp, vp, vp, vp, vp, vp, ll, ll, vp, vp, vp]),
     "unet_vec_emit": (i, [vp, vp, i, i, vp, vp, vp, ll, ll, vp, vp]),
+    "unet_simp_marks": (i, [vp, vp, vp, vp, i, i, ll, vp, vp]),
+    "unet_simp_gather": (i, [vp, vp, vp, vp, vp, ll, ll, ll, vp, vp, vp]),
+    "unet_simp_closed": (i, [vp, vp, vp, vp, vp, ll, ll, i, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "unet_simp_near_rounds": (i, [ll, vp, vp, vp, vp, i, vp, vp]),
+    "unet_simp_dp_rounds": (i, [vp, vp, vp, ll, ll, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "unet_simp_emit": (i, [vp, vp, vp, vp, vp, vp, vp, ll, ll, ll, vp, vp, vp]),
+    "unet_simp_area": (i, [vp, vp, vp, ll, ll, vp, vp]),
 }
 # bf16-storage twins: same argument lists (every tensor is a void pointer on this side)
 for _n in ("bn_stats", "affine_act", "bn_bwd_reduce", "bn_bwd_apply", "maxpool3x3s2", "maxpool3x3s2_bwd", "avgpool2_ceil",

@@ -1617,6 +1617,126 @@ def vec_emit(flags: torch.Tensor, offs: torch.Tensor, corner: torch.Tensor, pos:
           "vec_emit")
 
 
+# ---------------------------------------------------------------------------------------------- ring simplification (csrc/simplify.hip)
+
+SIMP_MAX_Q = 16 * 4096          # the tolerance in sixteenths of a pixel
+
+
+def _simp_rounds(what: str, rounds, changed: torch.Tensor) -> int:
+    if isinstance(rounds, bool) or not isinstance(rounds, int) or not 0 <= rounds <= 64:
+        raise ValueError(f"{what}: rounds must be an int in 0..64, got {rounds!r}")
+    _pp_tensor(what, "changed", changed, torch.int32, numel=max(rounds, 1))
+    return rounds
+
+
+def simp_marks(labels: torch.Tensor, flags: torch.Tensor, offs: torch.Tensor, corner: torch.Tensor, E: int, cand: torch.Tensor):
+    """cand[e] (uint8): bit 0 = the end vertex of edge e is a corner or a node, bit 4 = it is a node (unet_hip.h)"""
+    _pp_tensor("simp_marks", "labels", labels, torch.int32, labels.shape)
+    _pp_tensor("simp_marks", "flags", flags, torch.uint8, labels.shape)
+    _pp_tensor("simp_marks", "offs", offs, torch.int32, labels.shape)
+    _vec_count("simp_marks", "E", E)
+    _pp_tensor("simp_marks", "corner", corner, torch.uint8, numel=E)
+    _pp_tensor("simp_marks", "cand", cand, torch.uint8, numel=E)
+    H, W = labels.shape
+    check(lib.unet_simp_marks(labels.data_ptr(), flags.data_ptr(), offs.data_ptr(), corner.data_ptr(), H, W, E, cand.data_ptr(), _stream()), "simp_marks")
+
+
+def simp_gather(ring: torch.Tensor, ridx: torch.Tensor, pos: torch.Tensor, coff: torch.Tensor, cand: torch.Tensor, E: int, R: int, C_: int,
+                cring: torch.Tensor, cnode: torch.Tensor):
+    """cring[k] / cnode[k] = ring index / node mark of candidate k = coff[pos[e]]"""
+    for name, v in (("E", E), ("R", R), ("C", C_)):
+        _vec_count("simp_gather", name, v)
+    for name, t in (("ring", ring), ("ridx", ridx), ("pos", pos), ("coff", coff)):
+        _pp_tensor("simp_gather", name, t, torch.int32, numel=E)
+    _pp_tensor("simp_gather", "cand", cand, torch.uint8, numel=E)
+    _pp_tensor("simp_gather", "cring", cring, torch.int32, numel=C_)
+    _pp_tensor("simp_gather", "cnode", cnode, torch.uint8, numel=C_)
+    check(lib.unet_simp_gather(ring.data_ptr(), ridx.data_ptr(), pos.data_ptr(), coff.data_ptr(), cand.data_ptr(), E, R, C_, cring.data_ptr(),
+                               cnode.data_ptr(), _stream()), "simp_gather")
+
+
+def simp_closed(cxy: torch.Tensor, cring: torch.Tensor, cnode: torch.Tensor, cs: torch.Tensor, cn: torch.Tensor, C_: int, R: int, W: int,
+                nnodes: torch.Tensor, keys: torch.Tensor, keep: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor):
+    """anchors and far points of the rings with fewer than two nodes, then keep / lo / hi (unet_hip.h); keys: int64 [3, R] work words"""
+    _vec_count("simp_closed", "C", C_)
+    _vec_count("simp_closed", "R", R)
+    _vec_count("simp_closed", "W", W)
+    _pp_tensor("simp_closed", "cxy", cxy, torch.int32, numel=2 * C_)
+    _pp_tensor("simp_closed", "cring", cring, torch.int32, numel=C_)
+    _pp_tensor("simp_closed", "cnode", cnode, torch.uint8, numel=C_)
+    for name, t in (("cs", cs), ("cn", cn), ("nnodes", nnodes)):
+        _pp_tensor("simp_closed", name, t, torch.int32, numel=R)
+    _pp_tensor("simp_closed", "keys", keys, torch.int64, numel=3 * R)
+    if tuple(keys.shape) != (3, R):
+        raise ValueError(f"simp_closed: keys has shape {tuple(keys.shape)}, expected {(3, R)}")
+    _pp_tensor("simp_closed", "keep", keep, torch.uint8, numel=C_)
+    _pp_tensor("simp_closed", "lo", lo, torch.int32, numel=C_)
+    _pp_tensor("simp_closed", "hi", hi, torch.int32, numel=C_)
+    check(lib.unet_simp_closed(cxy.data_ptr(), cring.data_ptr(), cnode.data_ptr(), cs.data_ptr(), cn.data_ptr(), C_, R, W, nnodes.data_ptr(),
+                               keys[0].data_ptr(), keys[1].data_ptr(), keys[2].data_ptr(), keep.data_ptr(), lo.data_ptr(), hi.data_ptr(), _stream()),
+          "simp_closed")
+
+
+def simp_near_rounds(C_: int, a, b, rounds: int, changed: torch.Tensor):
+    """`rounds` doubling rounds of the nearest-kept search between the sets a = (lo, hi) and b; changed[r] = 1 if round r changed a pointer"""
+    _vec_count("simp_near_rounds", "C", C_)
+    for t in (*a, *b):
+        _pp_tensor("simp_near_rounds", "a / b", t, torch.int32, numel=C_)
+    _simp_rounds("simp_near_rounds", rounds, changed)
+    check(lib.unet_simp_near_rounds(C_, a[0].data_ptr(), a[1].data_ptr(), b[0].data_ptr(), b[1].data_ptr(), rounds, changed.data_ptr(), _stream()),
+          "simp_near_rounds")
+
+
+def simp_dp_rounds(cxy: torch.Tensor, cring: torch.Tensor, cn: torch.Tensor, C_: int, R: int, W: int, q: int, first: bool, rounds: int,
+                   keep: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor, key: torch.Tensor, slot: torch.Tensor, win: torch.Tensor,
+                   changed: torch.Tensor):
+    """`rounds` Douglas-Peucker rounds at tolerance q / 16 pixels (unet_hip.h); changed[r] = 1 if round r still had a live segment"""
+    _vec_count("simp_dp_rounds", "C", C_)
+    _vec_count("simp_dp_rounds", "R", R)
+    _vec_count("simp_dp_rounds", "W", W)
+    if isinstance(q, bool) or not isinstance(q, int) or not 0 <= q <= SIMP_MAX_Q:
+        raise ValueError(f"simp_dp_rounds: q must be an int in 0..{SIMP_MAX_Q}, got {q!r}")
+    _pp_tensor("simp_dp_rounds", "cxy", cxy, torch.int32, numel=2 * C_)
+    _pp_tensor("simp_dp_rounds", "cn", cn, torch.int32, numel=R)
+    _pp_tensor("simp_dp_rounds", "keep", keep, torch.uint8, numel=C_)
+    for name, t in (("cring", cring), ("lo", lo), ("hi", hi), ("win", win)):
+        _pp_tensor("simp_dp_rounds", name, t, torch.int32, numel=C_)
+    for name, t in (("key", key), ("slot", slot)):
+        _pp_tensor("simp_dp_rounds", name, t, torch.int64, numel=C_)
+    _simp_rounds("simp_dp_rounds", rounds, changed)
+    check(lib.unet_simp_dp_rounds(cxy.data_ptr(), cring.data_ptr(), cn.data_ptr(), C_, R, W, q, int(bool(first)), rounds, keep.data_ptr(), lo.data_ptr(),
+                                  hi.data_ptr(), key.data_ptr(), slot.data_ptr(), win.data_ptr(), changed.data_ptr(), _stream()), "simp_dp_rounds")
+
+
+def simp_emit(cxy: torch.Tensor, cring: torch.Tensor, keep: torch.Tensor, koff: torch.Tensor, kstart: torch.Tensor, vbase: torch.Tensor,
+              newring: torch.Tensor, C_: int, R: int, V: int, xy: torch.Tensor, vring: torch.Tensor):
+    """xy / vring: the kept candidates of the rings with newring[r] >= 0, at vbase[r] + koff[k] - kstart[r]"""
+    for name, v in (("C", C_), ("R", R), ("V", V)):
+        _vec_count("simp_emit", name, v)
+    _pp_tensor("simp_emit", "cxy", cxy, torch.int32, numel=2 * C_)
+    _pp_tensor("simp_emit", "keep", keep, torch.uint8, numel=C_)
+    for name, t in (("cring", cring), ("koff", koff)):
+        _pp_tensor("simp_emit", name, t, torch.int32, numel=C_)
+    for name, t in (("kstart", kstart), ("newring", newring)):
+        _pp_tensor("simp_emit", name, t, torch.int32, numel=R)
+    _pp_tensor("simp_emit", "vbase", vbase, torch.int64, numel=R)
+    _pp_tensor("simp_emit", "xy", xy, torch.int32, numel=2 * V)
+    _pp_tensor("simp_emit", "vring", vring, torch.int32, numel=V)
+    check(lib.unet_simp_emit(cxy.data_ptr(), cring.data_ptr(), keep.data_ptr(), koff.data_ptr(), kstart.data_ptr(), vbase.data_ptr(), newring.data_ptr(),
+                             C_, R, V, xy.data_ptr(), vring.data_ptr(), _stream()), "simp_emit")
+
+
+def simp_area(xy: torch.Tensor, vring: torch.Tensor, ring_start: torch.Tensor, V: int, R: int, area2: torch.Tensor):
+    """area2[r] (int64) = twice the signed area of ring r of the result"""
+    _vec_count("simp_area", "V", V)
+    _vec_count("simp_area", "R", R)
+    _pp_tensor("simp_area", "xy", xy, torch.int32, numel=2 * V)
+    _pp_tensor("simp_area", "vring", vring, torch.int32, numel=V)
+    _pp_tensor("simp_area", "ring_start", ring_start, torch.int64, numel=R + 1)
+    _pp_tensor("simp_area", "area2", area2, torch.int64, numel=R)
+    check(lib.unet_simp_area(xy.data_ptr(), vring.data_ptr(), ring_start.data_ptr(), V, R, area2.data_ptr(), _stream()), "simp_area")
+
+
 # ---------------------------------------------------------------------------------------------- GeoTIFF strips on the device (csrc/tiff_encode.hip)
 
 def tiff_lzw_cap(n: int) -> int:

@@ -28,10 +28,52 @@ most ceil(log2 E) + 1 rounds, in groups after each of which one word says whethe
 call: E, R, V, P and those words.  Ring- and polygon-level bookkeeping (a sort and a few scans over R entries) uses torch.
 
 Memory: 10 bytes per pixel (labels 4, flags 1, edge offsets 4, the mask 1) and 42 bytes per edge (six int32 arrays, two int64 arrays of
-area terms, two byte arrays), beside 28 bytes per ring and 8 per vertex.  Every buffer that a kernel writes comes from _alloc."""
+area terms, two byte arrays), beside 28 bytes per ring and 8 per vertex.  Every buffer that a kernel writes comes from _alloc.
+
+polygonize(mask, simplify=t) simplifies the rings on the device before they leave it (csrc/simplify.hip): a Douglas-Peucker
+on the ARCS between the junctions of the borders, in exact integer arithmetic, so that every shared border is simplified once and
+identically from both sides and neighbouring polygons keep one common border.  The result is a function of the mask, exclude and t alone;
+tests/simplify_ref.py restates the rules below in plain Python and the device arrays equal it bit for bit.  simplify=None launches what
+is described above and nothing else.  Crossings between two different simplified arcs and self-intersections at large tolerances
+(mapshaper's default behaviour as well), validity repair, Visvalingam simplification, dissolve by class and tolerances in map units are out
+of scope.
+
+Nodes       four unit segments meet at a pixel corner; a segment is a border if the two pixels beside it have different labels (those of
+            label_components; excluded classes are labelled like any other; outside the raster is one label of its own).  A corner is
+            a node if at least 3 of its segments are borders (T-junctions, crossings, saddle vertices) or if it is one of the four raster
+            corners.  Nodes are never removed.
+Candidates  of a ring: its corner vertices and the nodes it passes -- a ring can run straight through a node (the far side of a
+            T-junction), which the plain rings do not list but these do -- in walk order from the leader on.
+Arcs        the run of candidates from one node to the next along a ring.  The two rings that share a border see the same arc in opposite
+            directions, so every choice below depends on geometry alone; the raster frame is exact (every frame arc is a straight
+            segment between nodes).  A ring without a node is one closed arc whose anchor is its candidate with the smallest (y, x); a
+            ring with one node has that node as anchor.  A closed arc is split at the candidate farthest from the anchor (squared
+            distance in int64, ties to the smallest (y, x)); that vertex is kept without a test and the halves are ordinary arcs.
+Douglas-Peucker  on an arc P .. Q: among the interior candidates Z the one with the largest |c|, c = (Q - P) x (Z - P) in int64, ties to
+            the smallest (y, x), is kept iff 256 c^2 > q^2 |Q - P|^2, evaluated in 128 bits, where q = floor(16 t + 0.5) is the tolerance
+            in sixteenths of a pixel, 0 <= t <= 4096.  This is the distance to the LINE through P and Q, not to the segment.  If Z is
+            kept both parts recurse, else the whole interior is dropped.  At t = 0 every candidate is kept.
+Afterwards  a ring with fewer than 3 vertices is dropped (both rings of a small island go together and its area falls to its
+            surroundings: a one-pixel island disappears from t = 0.75 on); a polygon whose exterior ring is dropped is dropped with its
+            holes (a hole that outlives its exterior is an orphan; the reference counts them).
+Result      Polygons of the same layout and orders: vertices in walk order from the leader on, rings by leader, polygons by label;
+            ring_area is recomputed from the kept vertices (half the shoelace sum, towards zero: integer vertices can enclose a
+            half-integer area), poly_pixels stays the true pixel count, edges is unchanged.
+
+Passes: node marks per edge; the candidates placed in ring order by the placement, scan and emit passes above; ring index and node mark
+per candidate; per-ring minima / maxima for the anchors and far points; the nearest kept candidate before and after each candidate (lo /
+hi, cyclic within the ring) by pointer doubling; then rounds, in groups of 8 after each of which the host reads one word per round: every
+live candidate takes |c| against its chord lo .. hi, a 64-bit atomic maximum per segment of (|c| << 32 | ~(y (W + 1) + x)) finds the winner
+with its tie-break (a maximum does not depend on the order of arrival), the winner is tested, and its segment splits there or dies.  The
+number of rounds is the recursion depth of the deepest arc.  Then the scan of the keep marks, the kept vertices of the surviving rings,
+and the areas (exact integer sums).  Extra host reads: one per group of rounds and the new totals; none per ring.
+Memory per candidate: 46 bytes (coordinates 8, ring index 4, node and keep marks 2, the four int32 lo / hi arrays of the two doubling sets
+16 -- two of them serve later as the winners and the vertex offsets --, the keys 8 and the per-segment maxima 8), beside one more byte per
+edge (the candidate marks; their ring-order copy and their scan reuse buffers of the tracer), 36 bytes per ring and 12 per kept vertex."""
 from __future__ import annotations
 
 import json
+import math
 import os
 import time
 from dataclasses import dataclass, fields
@@ -44,6 +86,8 @@ from . import ops
 from .postprocess import _is_int, _to_device
 
 _GROUP = 4                    # doubling rounds per host look at the convergence words
+_SIMPLIFY_GROUP = 8           # Douglas-Peucker rounds per host look
+MAX_TOLERANCE = 4096          # pixels
 
 
 def _alloc(shape, dtype, device) -> torch.Tensor:
@@ -64,9 +108,12 @@ class Polygons:
     poly_ring_start: torch.Tensor      # int64 [P + 1]
     poly_rings: torch.Tensor           # int64 [R]: ring indices, per polygon the exterior first, then the holes by leader
     edges: int = 0                     # boundary edges traced
+    raw_vertices: int = 0              # simplify: the vertices that polygonize gives without it (else 0)
+    candidates: int = 0                # simplify: corners and passed nodes = the vertices at tolerance 0 (else 0)
+    rounds: int = 0                    # simplify: Douglas-Peucker rounds = the recursion depth of the deepest arc (else 0)
 
     def cpu(self) -> "Polygons":
-        return Polygons(**{f.name: (getattr(self, f.name).cpu() if f.name != "edges" else self.edges) for f in fields(self)})
+        return Polygons(**{f.name: (v.cpu() if isinstance(v, torch.Tensor) else v) for f in fields(self) for v in (getattr(self, f.name),)})
 
     @property
     def n_polygons(self) -> int:
@@ -149,7 +196,100 @@ class _Stages:
             self.t = now
 
 
-def _polygonize(m: torch.Tensor, exclude: tuple, stages: Optional[dict] = None) -> Polygons:
+def check_simplify(simplify) -> Optional[int]:
+    """None | a tolerance in pixels, 0..4096 -> None | q = floor(16 tolerance + 0.5), the tolerance in sixteenths of a pixel"""
+    if simplify is None:
+        return None
+    if isinstance(simplify, bool) or not isinstance(simplify, (int, float, np.integer, np.floating)) or not math.isfinite(simplify):
+        raise ValueError(f"simplify must be None or a finite number of pixels, got {simplify!r}")
+    if not 0 <= simplify <= MAX_TOLERANCE:
+        raise ValueError(f"simplify must lie in 0..{MAX_TOLERANCE} pixels, got {simplify!r}")
+    return int(math.floor(16.0 * float(simplify) + 0.5))
+
+
+def _flags_of(changed: torch.Tensor, g: int) -> list:
+    """the changed words of g rounds (one host read; int32 pairs in int64 words)"""
+    words = ops.vec_read(changed, 0, (g + 1) // 2)
+    return [(words[r // 2] >> (32 * (r % 2))) & 0xFFFFFFFF for r in range(g)]
+
+
+def _simplify(st: _Stages, q: int, m, labels, flags, offs, corner, ring, steps, ridx, ring_base, ring_len, ring_label, ring_area, pos, free,
+              mark, blocks, changed, E: int, R: int) -> Polygons:
+    """the passes of DESIGN 3.19 on the traced rings; `free` (int32 [E]) and `mark` (uint8 [E]) are buffers the tracer no longer needs"""
+    dev = m.device
+    H, W = m.shape
+    i32, i64, u8 = torch.int32, torch.int64, torch.uint8
+    ch32 = changed.view(i32)
+    tail = lambda v: torch.tensor([v], dtype=i64, device=dev)          # noqa: E731
+    cand = _alloc((E,), u8, dev)
+    ops.simp_marks(labels, flags, offs, corner, E, cand)
+    st.mark("simp_marks")
+    cand_ord, coff = mark, free
+    ops.vec_place(ring, steps, ridx, ring_base, ring_len, cand, E, R, pos, cand_ord)
+    C = _scan_total(cand_ord, coff, blocks)
+    cxy, cring, cnode = _alloc((C, 2), i32, dev), _alloc((C,), i32, dev), _alloc((C,), u8, dev)
+    ops.vec_emit(flags, offs, cand, pos, coff, E, C, cxy)
+    ops.simp_gather(ring, ridx, pos, coff, cand, E, R, C, cring, cnode)
+    cs = coff[ring_base]
+    cn = torch.cat([cs[1:], tail(C).to(i32)]) - cs
+    st.mark("simp_candidates")
+    keep = _alloc((C,), u8, dev)
+    near = [_alloc((C,), i32, dev) for _ in range(4)]
+    ops.simp_closed(cxy, cring, cnode, cs, cn, C, R, W, _alloc((R,), i32, dev), _alloc((3, R), i64, dev), keep, near[0], near[1])
+    st.mark("simp_closed")
+    (lo, hi), (win, koff) = _doubling(C, lambda a, b, g: ops.simp_near_rounds(C, a, b, g, ch32), (near[0], near[1]), (near[2], near[3]), changed)
+    st.mark("simp_near")
+    key, slot = _alloc((C,), i64, dev), _alloc((C,), i64, dev)
+    rounds, first = 0, True
+    while rounds <= C:          # an arc of n candidates is settled after at most n rounds
+        ops.simp_dp_rounds(cxy, cring, cn, C, R, W, q, first, _SIMPLIFY_GROUP, keep, lo, hi, key, slot, win, ch32)
+        first = False
+        live = sum(1 for f in _flags_of(changed, _SIMPLIFY_GROUP) if f)
+        rounds += live
+        if live < _SIMPLIFY_GROUP:
+            break
+    st.mark("simp_rounds")
+    K = _scan_total(keep, koff, blocks)
+    kstart = koff[cs.to(i64)]
+    kcount = torch.cat([kstart[1:], tail(K).to(i32)]) - kstart
+
+    # ring and polygon level, in torch as in _polygonize: rings with fewer than 3 vertices go, and polygons whose exterior ring goes
+    order = torch.argsort(ring_label.to(i64) * R + torch.arange(R, dtype=i64, device=dev))
+    by_label = ring_label[order]
+    first_of = torch.ones(R, dtype=torch.bool, device=dev)
+    first_of[1:] = by_label[1:] != by_label[:-1]
+    starts = torch.nonzero(first_of).flatten()
+    poly = torch.cumsum(first_of.to(i64), 0) - 1
+    exterior = (kcount >= 3)[order[starts]]                              # the exterior ring of a polygon is its first ring by leader
+    stays = (kcount >= 3)[order] & exterior[poly]                        # in (label, leader) order
+    final = torch.zeros(R, dtype=torch.bool, device=dev)
+    final[order] = stays
+    newring = torch.where(final, torch.cumsum(final.to(i64), 0) - 1, torch.full((R,), -1, dtype=i64, device=dev)).to(i32)
+    count = torch.where(final, kcount, torch.zeros_like(kcount)).to(i64)
+    vbase = torch.cumsum(count, 0) - count
+    V, R2, raw = ops.vec_read(torch.stack([count.sum(), final.sum(), corner.sum(dtype=i64)]), 0, 3)          # a host read: the new totals
+    if V == 0:
+        out = _empty(dev)
+        out.edges, out.raw_vertices, out.candidates, out.rounds = E, raw, C, rounds
+        return out
+    xy, vring = _alloc((V, 2), i32, dev), _alloc((V,), i32, dev)
+    ops.simp_emit(cxy, cring, keep, koff, kstart, vbase, newring, C, R, V, xy, vring)
+    ring_start = torch.cat([vbase[final], tail(V)])
+    area2 = _alloc((R2,), i64, dev)
+    ops.simp_area(xy, vring, ring_start, V, R2, area2)
+    st.mark("simp_emit")
+    poly_ring_start = torch.cat([starts, tail(R)])
+    run = torch.cat([tail(0), torch.cumsum(ring_area[order], 0)])
+    pixels = run[poly_ring_start[1:]] - run[poly_ring_start[:-1]]          # the true pixel counts: the areas of the traced rings
+    run = torch.cat([tail(0), torch.cumsum(stays.to(i64), 0)])
+    rings_of = (run[poly_ring_start[1:]] - run[poly_ring_start[:-1]])[exterior]
+    poly_label = by_label[starts][exterior]
+    st.mark("simp_polygons")
+    return Polygons(xy, ring_start, ring_label[final], torch.div(area2, 2, rounding_mode="trunc"), poly_label, m.view(-1)[poly_label.to(i64)],
+                    pixels[exterior], torch.cat([tail(0), torch.cumsum(rings_of, 0)]), newring[order[stays]].to(i64), E, raw, C, rounds)
+
+
+def _polygonize(m: torch.Tensor, exclude: tuple, stages: Optional[dict] = None, q: Optional[int] = None) -> Polygons:
     st = _Stages(stages)
     dev = m.device
     H, W = m.shape
@@ -201,6 +341,10 @@ def _polygonize(m: torch.Tensor, exclude: tuple, stages: Optional[dict] = None) 
     ring_label, ring_len, ring_area = _alloc((R,), i32, dev), _alloc((R,), i64, dev), _alloc((R,), i64, dev)
     ops.vec_ring_info(flags, offs, labels, succ, ring, ridx, steps, area, E, R, ring_label, ring_len, ring_area)
     ring_base = torch.cumsum(ring_len, 0) - ring_len
+    if q is not None:
+        st.mark("ring_info")
+        return _simplify(st, q, m, labels, flags, offs, corner, ring, steps, ridx, ring_base, ring_len, ring_label, ring_area, free2, free0, mark,
+                         blocks, changed, E, R)
     pos, corner_ord = free2, mark
     ops.vec_place(ring, steps, ridx, ring_base, ring_len, corner, E, R, pos, corner_ord)
     voff = free0
@@ -224,14 +368,18 @@ def _polygonize(m: torch.Tensor, exclude: tuple, stages: Optional[dict] = None) 
                     poly_ring_start, order, E)
 
 
-def polygonize(mask, exclude=None, stages: Optional[dict] = None) -> Polygons:
+def polygonize(mask, exclude=None, simplify=None, stages: Optional[dict] = None) -> Polygons:
     """Polygons (device tensors) of the 4-connected components of a contiguous uint8 [H, W] class mask (device tensor, host tensor or NumPy
     array; host input is uploaded).  exclude: None, an int or an iterable of class ids 0..255 whose components get no polygon.
     Connectivity 8 is not offered: its components pinch at vertices and holes would need a point-in-polygon assignment.
-    stages: a dict that receives the milliseconds of every stage (this synchronises the device after each: for measurements only)."""
+    simplify: None, or the tolerance in pixels (0..4096) of the arc-based Douglas-Peucker simplification of the module docstring; None
+    launches what it launched before the simplification existed.
+    stages: a dict that receives the milliseconds of every stage (this synchronises the device after each: for measurements only); with
+    simplify the stages after the ring info are ring_info and simp_*."""
     exclude = check_exclude(exclude)
+    q = check_simplify(simplify)
     m, _ = _to_device(mask, torch.uint8, "polygonize")
-    return _polygonize(m, exclude, stages)
+    return _polygonize(m, exclude, stages, q)
 
 
 # ------------------------------------------------------------------------------------------------------------------ GeoJSON (host)
@@ -317,13 +465,17 @@ def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, co
 # ------------------------------------------------------------------------------------------------------------------ entry points
 
 def check_vector(vector, vector_exclude=None, regression: bool = False, all_classes: bool = False, specific_class=None, large_file: bool = False,
-                 merge: bool = True, class_zero: bool = False) -> Optional[tuple]:
+                 merge: bool = True, class_zero: bool = False, simplify=None) -> Optional[tuple]:
     """the vector_path= / vector= and vector_exclude= arguments of predict_raster / save_predictions, validated before the model is loaded or
-    anything touches the GPU -> the classes to exclude (a tuple), or None when no vector file is wanted"""
+    anything touches the GPU -> the classes to exclude (a tuple), or None when no vector file is wanted.  simplify (vector_simplify=): None or
+    a finite tolerance of 0..4096 pixels, only with a vector output"""
     if vector is None or vector is False:
         if vector_exclude is not None:
             raise ValueError("vector_exclude without a vector output")
+        if simplify is not None:
+            raise ValueError("vector_simplify without a vector output")
         return None
+    check_simplify(simplify)
     exclude = check_exclude(vector_exclude)
     if regression or all_classes or specific_class is not None:
         raise ValueError("a vector output needs the class mask: not with regression, all_classes or specific_class")
@@ -336,11 +488,14 @@ def check_vector(vector, vector_exclude=None, regression: bool = False, all_clas
     return exclude
 
 
-def vectorize_mask(mask, path, exclude=(), geotransform=None, epsg=None, codes=None, class_zero: bool = False, timing: Optional[dict] = None) -> Polygons:
-    """polygonize + write_geojson of an assembled class mask (device or host); timing gains vector_seconds / _polygons / _vertices"""
+def vectorize_mask(mask, path, exclude=(), geotransform=None, epsg=None, codes=None, class_zero: bool = False, timing: Optional[dict] = None,
+                   simplify=None) -> Polygons:
+    """polygonize + write_geojson of an assembled class mask (device or host); timing gains vector_seconds / _polygons / _vertices and
+    vector_vertices_raw (the vertices before the simplification; equal to vector_vertices without one)"""
     t0 = time.perf_counter()
-    polys = polygonize(mask, exclude)
+    polys = polygonize(mask, exclude, simplify)
     n = write_geojson(path, polys, geotransform, epsg, codes, class_zero)
     if timing is not None:
-        timing.update(vector_seconds=time.perf_counter() - t0, vector_polygons=n, vector_vertices=polys.n_vertices)
+        timing.update(vector_seconds=time.perf_counter() - t0, vector_polygons=n, vector_vertices=polys.n_vertices,
+                      vector_vertices_raw=polys.n_vertices if simplify is None else polys.raw_vertices)
     return polys
