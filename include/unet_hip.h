@@ -656,6 +656,8 @@ int unet_cast_slice_bf16(const float* x, int x_cs, int x_co, unet_bf16* y, int y
  * not merged, give-up code, 0}.  frozen_class: -1 (none) or 0..255.  All workspace belongs to the caller.
  * unet_cc_label: labels[p] = the smallest linear index y * W + x of p's component (equal class, 4- / 8-adjacency); resets counters.
  *   Launches: tiles of unet_cc_tile_shape in LDS, border merge (atomicMin on the parent array = labels), flatten.
+ * unet_cc_label_keys: the same labelling, by the same kernels, of a contiguous uint32 [H, W] key image at 4-adjacency (a component = equal
+ *   keys): the flat zones of the instance split below.
  * unet_cc_sizes: sizes[l] = pixel count of the component with root label l, 0 at every other index.
  * unet_sieve_round: one round on `in`: label + sizes + per small component (size < min_pixels, class != frozen_class) the edge-adjacent
  *   component with the largest key (size << 32 | 0xFFFFFFFF - label), class != frozen_class, by a 64-bit atomicMax; a small component
@@ -668,6 +670,7 @@ int unet_cast_slice_bf16(const float* x, int x_cs, int x_co, unet_bf16* y, int y
  * Bad arguments return -1 before any launch. */
 void unet_cc_tile_shape(int* th, int* tw);
 int unet_cc_label(const uint8_t* mask, int H, int W, int connectivity, int32_t* labels, int32_t* counters, void* stream);
+int unet_cc_label_keys(const uint32_t* keys, int H, int W, int32_t* labels, int32_t* counters, void* stream);
 int unet_cc_sizes(const int32_t* labels, int H, int W, int32_t* sizes, void* stream);
 int unet_sieve_round(const uint8_t* in, uint8_t* out, int H, int W, int connectivity, long long min_pixels, int frozen_class,
                      int32_t* labels, int32_t* sizes, unsigned long long* keys, int32_t* counters, void* stream);
@@ -747,7 +750,8 @@ int unet_tiff_reduce_level(const void* src, int elem_size, int kind, int P, int 
 
 /* --------------------------------------------------------- polygon rings --
  * Ring tracing of a labelled class mask (csrc/vectorize.hip, unet_amd/vectorize.py).  mask / labels are contiguous [H, W] with
- * H * W <= 2^31 - 1, labels those of unet_cc_label at connectivity 4.  Sides: N=0 W=1 S=2 E=3; the dense id of an edge is 4 p + s, its
+ * H * W <= 2^31 - 1; labels are those of unet_cc_label at connectivity 4, or any other image in which every segment is 4-connected, of
+ * one class and labelled by the smallest linear index of its pixels (unet_inst_canonical writes such an image).  Sides: N=0 W=1 S=2 E=3; the dense id of an edge is 4 p + s, its
  * compact index offs[p] + popcount(flags[p] & ((1 << s) - 1)).  E edges, R rings, V vertices, all in 1..2^31 - 1.
  * vec_flags: flags[p] bit s = side s of pixel p is a boundary edge (the neighbour is outside or has another label); 0 where the
  *   pixel's class has its bit set in exclude8 (256 bits as 8 words, NULL: none).
@@ -822,6 +826,46 @@ int unet_simp_emit(const int32_t* cxy, const int32_t* cring, const uint8_t* keep
                    void* stream);
 int unet_simp_area(const int32_t* xy, const int32_t* vring, const long long* ring_start, long long V, long long R, long long* area2,
                    void* stream);
+
+/* --------------------------------------------------------- instance split --
+ * Touching objects of one class split along the ridges of a capped distance transform (csrc/instances.hip, unet_amd/instances.py, DESIGN
+ * 3.20, where the rules are).  mask is a contiguous uint8 [H, W], H * W <= 2^31 - 1 = n; every other image is [H, W] of the type given.
+ * A zone / segment is named by the linear index of one of its pixels, its root (root[p] == p there); per-zone and per-segment arrays are
+ * pixel-sized and used at the roots only.  partial: unet_inst_partials() int64 words; their sum is the count the call reports.
+ * inst_distance: keys[p] = class << 16 | h(p), h = min(R^2, squared distance to the nearest pixel of another value inside the raster) for
+ *   the classes of split8 (256 bits as 8 words), 0 for the others.  Two launches: g (uint8 workspace) = the horizontal distance capped at R
+ *   = radius (1..255), 4 x 256 px per block with 4 x (256 + 510) bytes of LDS; then columns, 64 x 32 px per block with (64 + 2 R) x 32 x 2
+ *   bytes of dynamic LDS.  unet_inst_tile_shapes gives those tile sizes.
+ * inst_check_labels: *bad = 1 unless for every p: 0 <= labels[p] <= p, labels[labels[p]] == labels[p], mask[labels[p]] == mask[p].
+ * inst_ascent: zone = unet_cc_label_keys(keys).  zkey[Z] = max over the pixels u 4-adjacent to a pixel of Z, of Z's class and higher than Z,
+ *   of (h(u) << 32 | ~u); ptr[Z] = zone[u] of that maximum, or Z for a zone without one (a seed).  partial: seeds.
+ * inst_ptr_rounds: `rounds` (0..64) Jacobi rounds b[r] = a[a[r]] at the roots r of `root`, reading ptr_a in even rounds and ptr_b in odd ones;
+ *   changed[k] = 1 if round k moved a pointer (the words of vec_min_rounds).  A round behind one that moved nothing returns at once: both
+ *   buffers hold the settled pointers then, and its own word stays 0.
+ * inst_gather: out[p] = ptr[root[p]]; out may be root.
+ * inst_merge_round: on the segments seg (updated in place): peak[A] = max h; best[A] = max over the 4-adjacent pairs (p in A, r in B != A) of
+ *   equal class of (min(h(p), h(r)) << 32 | ~B); A points to B = best(A) iff 256 (peak - pass) - q^2 = L gives L < 0 or L^2 < 1024 q^2 pass
+ *   (int64; q = depth in sixteenths of a pixel, 0..4080) and (peak(A), -A) < (peak(B), -B); `doublings` (1..32, at least log2 of the segment
+ *   count) rounds of inst_ptr_rounds, with their words in changed (`doublings` words), follow every chain to its end, then
+ *   seg[p] = ptr[seg[p]].  partial: the segments that merged.
+ * inst_canonical: lowest[A] = the smallest p in A (atomic minimum), labels[p] = lowest[seg[p]].  partial: segments.
+ * inst_marks / inst_ids: mark[p] = 1 where labels[p] == p and the class is in split8; with offs = unet_vec_scan(mark), ids[p] = offs[labels[p]]
+ *   + 1 for the classes of split8 and 0 for the others: dense ids in ascending label order.
+ * Atomics take maxima and minima of integers only.  Bad arguments return -1 before any launch. */
+void unet_inst_tile_shapes(int* row_th, int* row_tw, int* col_th, int* col_tw);
+int unet_inst_partials(void);
+int unet_inst_distance(const uint8_t* mask, int H, int W, const uint32_t* split8, int radius, uint8_t* g, uint32_t* keys, void* stream);
+int unet_inst_check_labels(const uint8_t* mask, const int32_t* labels, int H, int W, long long* bad, void* stream);
+int unet_inst_ascent(const uint32_t* keys, const int32_t* zone, int H, int W, unsigned long long* zkey, int32_t* ptr, long long* partial,
+                     void* stream);
+int unet_inst_ptr_rounds(const int32_t* root, long long n, int32_t* ptr_a, int32_t* ptr_b, int rounds, int32_t* changed, void* stream);
+int unet_inst_gather(const int32_t* root, const int32_t* ptr, long long n, int32_t* out, void* stream);
+int unet_inst_merge_round(const uint32_t* keys, int32_t* seg, int H, int W, int q, int doublings, int32_t* peak, unsigned long long* best,
+                          int32_t* ptr_a, int32_t* ptr_b, int32_t* changed, long long* partial, void* stream);
+int unet_inst_canonical(const int32_t* seg, long long n, int32_t* lowest, int32_t* labels, long long* partial, void* stream);
+int unet_inst_marks(const uint8_t* mask, const int32_t* labels, long long n, const uint32_t* split8, uint8_t* mark, void* stream);
+int unet_inst_ids(const uint8_t* mask, const int32_t* labels, const int32_t* offs, long long n, const uint32_t* split8, uint32_t* ids,
+                  void* stream);
 
 #ifdef __cplusplus
 }

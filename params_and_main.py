@@ -96,12 +96,18 @@ VECTOR_EXCLUDE = None
 # VECTOR_SIMPLIFY None | a tolerance in pixels (0..4096): the rings are simplified on the GPU (Douglas-Peucker per shared border, so that
 # neighbouring polygons keep one common border) before they are written
 VECTOR_SIMPLIFY = None
+# touching objects of a class split into instances on the GPU (merge = True, class output; needs VECTOR, INSTANCES_RASTER or both): INSTANCES
+# None | a dict of unet_amd.instances.Instances arguments, e.g. {"classes": [2], "radius": 64, "min_depth": 2.0} = split class 2 along the
+# ridges of its distance transform (capped at 64 px) and merge basins shallower than 2 px back; the GeoJSON then has one feature per
+# instance.  INSTANCES_RASTER False | True: <merged raster stem>_instances.tif, a uint32 raster of the instance ids (0 off the split classes)
+INSTANCES = None
+INSTANCES_RASTER = False
 
 
 def main():
     global large_file, specific_class, all_classes, transforms, VALID_SCENES, self_attention, monitor, loss_func, LR_FINDER
     global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS
-    global VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY
+    global VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY, INSTANCES, INSTANCES_RASTER
     t0 = time.time()
     if enable_extra_parameters:          # params_and_main.py:129-145
         import warnings
@@ -113,6 +119,7 @@ def main():
         ARCHITECTURE, self_attention = xresnet34, False
         TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS = None, "mean", None, None, None, None
         VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY = False, None, None
+        INSTANCES, INSTANCES_RASTER = None, False
     if Create_tiles:
         from create_tiles_unet import split_raster
         split_raster(path_to_raster=image_path, path_to_mask=mask_path, base_dir=base_dir, patch_size=patch_size,
@@ -137,6 +144,8 @@ def main():
             extra["vector"], extra["vector_exclude"] = True, VECTOR_EXCLUDE
             if VECTOR_SIMPLIFY is not None:
                 extra["vector_simplify"] = VECTOR_SIMPLIFY
+        if INSTANCES is not None:
+            extra["instances"], extra["instances_raster"] = INSTANCES, INSTANCES_RASTER
         save_predictions(predict_model, predict_path, regression, merge, all_classes, specific_class, large_file, AOI, year,
                          validation_vision, class_zero, tta=TTA, **extra)
     print(f"Operation completed in {(time.time() - t0) / 60:.2f} minutes.")

@@ -67,6 +67,7 @@ from unet_amd.mosaic import MergePlan, blend_profile, check_blend, keep_windows,
 from unet_amd.tiffio import check_compress, check_tiling, read_tiff, resolve_overviews, tiff_info, write_tiff
 from unet_amd.tta import parse as tta_codes
 from unet_amd.vectorize import check_vector, epsg_of_tags, vectorize_mask
+from unet_amd.instances import check_instances
 
 
 def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_zero=False, compress=None, predictor=1,
@@ -92,6 +93,21 @@ def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_ze
                    overviews=overviews)
     if timing is not None:
         timing.update(write_seconds=time.perf_counter() - t0, file_bytes=os.path.getsize(output_file))
+
+
+def _run_instances(inst, out, dev, path, geotrans, tags, compress, predictor, tile, timing):
+    """the instance split of the assembled class mask `out` (a tensor, on the device or the host) -> (the mask on the device, labels, ids);
+    path: None, or the uint32 GeoTIFF of the dense ids (0 off the split classes) with the mask's geo tags, written by tiffio.write_tiff, so
+    compress="lzw", predictor=2 and tile= apply to it as to the mask"""
+    m = torch.as_tensor(out)
+    m = (m if m.is_cuda else m.to(dev)).contiguous()
+    labels, ids, _ = inst.run(m, timing)
+    if path is not None:
+        t0 = time.perf_counter()
+        write_tiff(path, ids.cpu().numpy().view(np.uint32), geotransform=geotrans, tags=tags, compress=compress, predictor=predictor, tile=tile)
+        if timing is not None:
+            timing.update(instances_write_seconds=time.perf_counter() - t0, instances_file_bytes=os.path.getsize(path))
+    return m, labels, ids
 
 
 def _geo(path):
@@ -393,7 +409,8 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                    regression: bool = False, all_classes: bool = False, specific_class: Optional[int] = None, large_file: bool = False,
                    batch_size: int = 16, out_path=None, class_zero: bool = False, timing: Optional[dict] = None,
                    batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
-                   return_array: bool = True, tile=None, overviews=None, vector_path=None, vector_exclude=None, vector_simplify=None):
+                   return_array: bool = True, tile=None, overviews=None, vector_path=None, vector_exclude=None, vector_simplify=None,
+                   instances=None, instances_path=None):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -437,6 +454,13 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     vector_simplify  None | a tolerance in pixels, 0..4096 (needs vector_path): the rings are simplified on the device before they are written,
              by a Douglas-Peucker on the arcs between the junctions of the borders, so that neighbouring polygons keep one common border
              (unet_amd/vectorize.py); polygons that shrink to fewer than 3 vertices get no feature.  timing gains vector_vertices_raw
+    instances  None | Instances | dict of its arguments (unet_amd/instances.py: classes, radius=64, min_depth=2.0): touching objects of the
+             named classes (the model's ids) are split into instances on the device, after postprocess and on the same tensor, so the
+             result does not depend on the rank count.  Needs vector_path, instances_path or both; only for the class mask and not with
+             large_file (ValueError).  With vector_path the GeoJSON has one feature per instance, with the added property `instance`, the
+             id of the instance raster (0 for components of classes that are not split).  timing gains instances_seconds and instances
+    instances_path  None | path of a uint32 GeoTIFF (needs instances): a dense id 1..N, in ascending label order, on every pixel of a
+             split class and 0 elsewhere, with the geo tags of the mask; compress, predictor and tile apply to it (host encoder)
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
@@ -445,6 +469,9 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
     tile, overviews = _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file)
     vec = check_vector(vector_path, vector_exclude, regression, all_classes, specific_class, large_file, True, class_zero, vector_simplify)
+    if instances is None and instances_path is not None:
+        raise ValueError("instances_path without instances")
+    inst = check_instances(instances, regression, all_classes, specific_class, large_file, True, vec is not None or instances_path is not None)
     if not return_array and out_path is None and vec is None:
         raise ValueError("return_array=False needs out_path: the prediction would go nowhere")
     model = getattr(model, "model", model)
@@ -489,10 +516,14 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     keep_out = compress is not None and out_path is not None          # the encoder takes the array where the merge assembled it
     with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
         out = _run_merge(model, places, MH, MW, regression, bool(large_file and not regression), rank, world, batch_size, make_input, want, timing,
-                         codes, blend, post, keep_out or vec is not None)
+                         codes, blend, post, keep_out or vec is not None or inst is not None)
     ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
+    labels = ids = None
+    if rank == 0 and inst is not None:
+        out, labels, ids = _run_instances(inst, out, dev, instances_path, ogt, tags, compress, predictor, tile, timing)
     if rank == 0 and vec is not None:
-        vectorize_mask(out, vector_path, vec, ogt, epsg_of_tags(tags), None, class_zero, timing, vector_simplify)
+        vectorize_mask(out, vector_path, vec, ogt, epsg_of_tags(tags), None, class_zero, timing, vector_simplify, labels, ids)
+    if rank == 0 and (vec is not None or inst is not None):
         if not keep_out and isinstance(out, torch.Tensor):
             out = out.cpu().numpy()
     if rank == 0 and out_path is not None:
@@ -655,7 +686,8 @@ def _tile_windows(batch_size: int, device, div255_twice: bool) -> Callable:
 def save_predictions(predict_model, predict_path, regression, merge=False, all_classes=False, specific_class=None, large_file=False,
                      AOI=None, year=None, validation_vision=True, class_zero=False, batch_size=16, timing: Optional[dict] = None,
                      batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
-                     tile=None, overviews=None, vector: bool = False, vector_exclude=None, vector_simplify=None):
+                     tile=None, overviews=None, vector: bool = False, vector_exclude=None, vector_simplify=None, instances=None,
+                     instances_raster: bool = False):
     """tta: None | "flips" | "d4" | a tuple of D4 codes (see predict_raster and unet_amd/tta.py), merged and per-tile outputs alike.
     blend: "mean" | "gaussian" (see predict_raster): how the windows of a merged prediction combine; only with merge=True (per-tile
     outputs have no overlap) and not with large_file (ValueError before the model is loaded).
@@ -668,12 +700,18 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     vector / vector_exclude (see predict_raster's vector_path): True writes <merged raster stem>.geojson beside the merged raster, with the
     class names of the model's vocab; only with merge=True, for the class mask and not with large_file (ValueError before the model is loaded).
     vector_simplify: None | a tolerance in pixels (see predict_raster); needs vector=True.
+    instances / instances_raster (see predict_raster's instances / instances_path): the instance split of the merged class mask; True writes
+    <merged raster stem>_instances.tif beside the merged raster.  Needs merge=True and vector=True, instances_raster=True or both
+    (ValueError before the model is loaded).
     validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
     check_blend(blend, large_file, merge)
     post = check_postprocess(postprocess, regression, all_classes, specific_class, merge)
     check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
     tile, overviews = _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file)
     vec = check_vector(vector or None, vector_exclude, regression, all_classes, specific_class, large_file, merge, class_zero, vector_simplify)
+    if instances is None and instances_raster:
+        raise ValueError("instances_raster without instances")
+    inst = check_instances(instances, regression, all_classes, specific_class, large_file, merge, vec is not None or bool(instances_raster))
     rank, local_rank, world = _dist_ctx()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model
@@ -692,7 +730,7 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     if merge:
         out, gt = _save_merged(model, tiles, geos, windows, rank, world, regression, _want(regression, all_classes, specific_class),
                                bool(large_file and not regression), batch_size, batch_invariant, codes, blend, timing, post,
-                               compress is not None or vec is not None)
+                               compress is not None or vec is not None or inst is not None)
     else:
         _save_tiles(model, tiles, geos, windows, rank, world, output_folder, regression, all_classes, specific_class, large_file, class_zero,
                     batch_size, batch_invariant, codes, compress, predictor)
@@ -707,10 +745,16 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     if rank != 0:
         return None
     name = "_".join(filter(None, [AOI, year, model_name, "prediction"])) + ".tif"
+    labels = ids = None
+    if inst is not None:
+        ipath = output_folder / (Path(name).stem + "_instances.tif") if instances_raster else None
+        out, labels, ids = _run_instances(inst, out, model._device, ipath, gt, geos[0][1], compress, predictor, tile, timing)
     if vec is not None:
         vocab = getattr(learn.dls, "vocab", None)
         names = list(vocab) if vocab is not None and len(vocab) >= model.n_out else None
-        vectorize_mask(out, (output_folder / name).with_suffix(".geojson"), vec, gt, epsg_of_tags(geos[0][1]), names, class_zero, timing, vector_simplify)
+        vectorize_mask(out, (output_folder / name).with_suffix(".geojson"), vec, gt, epsg_of_tags(geos[0][1]), names, class_zero, timing, vector_simplify,
+                       labels, ids)
+    if vec is not None or inst is not None:
         if compress is None and isinstance(out, torch.Tensor):
             out = out.cpu().numpy()
     store_tif(output_folder / name, out, gt, geos[0][1], -9999 if regression else None, class_zero, compress, predictor, timing, tile, overviews)

@@ -249,6 +249,7 @@ _sig = {
     "unet_mosaic_finalize_rows_weighted": (i, [vp, vp, vp, i, i, i, i, i, vp, c_float_p, vp]),
     "unet_cc_tile_shape": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "unet_cc_label": (i, [vp, i, i, i, vp, vp, vp]),
+    "unet_cc_label_keys": (i, [vp, i, i, vp, vp, vp]),
     "unet_cc_sizes": (i, [vp, i, i, vp, vp]),
     "unet_sieve_round": (i, [vp, vp, i, i, i, ll, i, vp, vp, vp, vp, vp]),
     "unet_majority_filter": (i, [vp, vp, i, i, i, i, vp]),
@@ -275,6 +276,17 @@ _sig = {
     "unet_simp_dp_rounds": (i, [vp, vp, vp, ll, ll, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]),
     "unet_simp_emit": (i, [vp, vp, vp, vp, vp, vp, vp, ll, ll, ll, vp, vp, vp]),
     "unet_simp_area": (i, [vp, vp, vp, ll, ll, vp, vp]),
+    "unet_inst_tile_shapes": (None, [C.POINTER(C.c_int)] * 4),
+    "unet_inst_partials": (i, []),
+    "unet_inst_distance": (i, [vp, i, i, C.POINTER(C.c_uint32), i, vp, vp, vp]),
+    "unet_inst_check_labels": (i, [vp, vp, i, i, vp, vp]),
+    "unet_inst_ascent": (i, [vp, vp, i, i, vp, vp, vp, vp]),
+    "unet_inst_ptr_rounds": (i, [vp, ll, vp, vp, i, vp, vp]),
+    "unet_inst_gather": (i, [vp, vp, ll, vp, vp]),
+    "unet_inst_merge_round": (i, [vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, vp]),
+    "unet_inst_canonical": (i, [vp, ll, vp, vp, vp, vp]),
+    "unet_inst_marks": (i, [vp, vp, ll, C.POINTER(C.c_uint32), vp, vp]),
+    "unet_inst_ids": (i, [vp, vp, vp, ll, C.POINTER(C.c_uint32), vp, vp]),
 }
 # bf16-storage twins: same argument lists (every tensor is a void pointer on this side)
 for _n in ("bn_stats", "affine_act", "bn_bwd_reduce", "bn_bwd_apply", "maxpool3x3s2", "maxpool3x3s2_bwd", "avgpool2_ceil",

@@ -1,5 +1,6 @@
 // Post-processing of a merged uint8 class mask on the device (unet_amd/postprocess.py):
 //   unet_cc_label         connected components of equal-class pixels (4- / 8-adjacency); label = smallest linear index of the component
+//   unet_cc_label_keys    the same components of a 32-bit key image at 4-adjacency (the flat zones of unet_amd/instances.py)
 //   unet_cc_sizes         pixel count of every component, stored at its root label
 //   unet_sieve_round      one round of the small-region sieve: label, sizes, best neighbour per small component, simultaneous merges
 //   unet_majority_filter  k x k majority vote (one Jacobi pass), window clipped to the raster
@@ -47,10 +48,13 @@ __device__ __forceinline__ void tile_union(int* L, int a, int b, int& budget) {
     }
 }
 
-__global__ __launch_bounds__(256) void cc_tile_kernel(const uint8_t* __restrict__ mask, int H, int W, int ntx, int conn8,
+// K: uint8_t, the class mask, or uint32_t, the (class << 16 | height) keys whose components are the flat zones of unet_inst_distance
+// (8 KiB of keys instead of 2 KiB of classes in LDS)
+template <typename K>
+__global__ __launch_bounds__(256) void cc_tile_kernel(const K* __restrict__ mask, int H, int W, int ntx, int conn8,
                                                      int* __restrict__ parent, int* __restrict__ counters) {
     __shared__ int L[CC_TP];
-    __shared__ uint8_t cls[CC_TP];
+    __shared__ K cls[CC_TP];
     const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
     const int y0 = ty * CC_TH, x0 = tx * CC_TW;
     const int t = threadIdx.x;
@@ -66,7 +70,7 @@ __global__ __launch_bounds__(256) void cc_tile_kernel(const uint8_t* __restrict_
     for (int i = t; i < CC_TP; i += 256) {
         const int ly = i / CC_TW, lx = i % CC_TW;
         if (y0 + ly >= H || x0 + lx >= W) continue;
-        const uint8_t c = cls[i];
+        const K c = cls[i];
         budget = 8 * CC_TP;          // the at most four unions of one pixel
         if (lx > 0 && cls[i - 1] == c) tile_union(L, i, i - 1, budget);
         if (ly > 0) {
@@ -113,7 +117,8 @@ __device__ __forceinline__ void global_union(int* P, int a, int b, long long& bu
 }
 
 // one thread per pixel in the first column (rows: first row) of a tile that has a tile to its left (above it)
-__global__ __launch_bounds__(256) void cc_border_kernel(const uint8_t* __restrict__ mask, int H, int W, int ntx, int nty, int conn8,
+template <typename K>
+__global__ __launch_bounds__(256) void cc_border_kernel(const K* __restrict__ mask, int H, int W, int ntx, int nty, int conn8,
                                                        int* __restrict__ parent, int* __restrict__ counters) {
     const long long n = (long long)H * W;
     const long long nv = (long long)(ntx - 1) * H, total = nv + (long long)(nty - 1) * W;
@@ -125,7 +130,7 @@ __global__ __launch_bounds__(256) void cc_border_kernel(const uint8_t* __restric
             x = (int)(i / H + 1) * CC_TW;
             y = (int)(i % H);
             const long long g = (long long)y * W + x;
-            const uint8_t c = mask[g];
+            const K c = mask[g];
             if (mask[g - 1] == c) global_union(parent, (int)g, (int)(g - 1), budget);
             if (conn8) {
                 if (y > 0 && mask[g - W - 1] == c) global_union(parent, (int)g, (int)(g - W - 1), budget);
@@ -136,7 +141,7 @@ __global__ __launch_bounds__(256) void cc_border_kernel(const uint8_t* __restric
             y = (int)(j / W + 1) * CC_TH;
             x = (int)(j % W);
             const long long g = (long long)y * W + x;
-            const uint8_t c = mask[g];
+            const K c = mask[g];
             if (mask[g - W] == c) global_union(parent, (int)g, (int)(g - W), budget);
             if (conn8) {
                 if (x > 0 && mask[g - W - 1] == c) global_union(parent, (int)g, (int)(g - W - 1), budget);
@@ -367,14 +372,15 @@ __global__ __launch_bounds__(256) void majority_kernel(const uint8_t* __restrict
 
 bool shape_ok(int H, int W) { return H > 0 && W > 0 && (long long)H * W <= 2147483647ll; }
 
-int label_launches(const uint8_t* mask, int H, int W, int connectivity, int32_t* labels, int32_t* counters, hipStream_t st) {
+template <typename K>
+int label_launches(const K* mask, int H, int W, int connectivity, int32_t* labels, int32_t* counters, hipStream_t st) {
     const int ntx = cdiv(W, CC_TW), nty = cdiv(H, CC_TH);
     const long long n = (long long)H * W;
-    hipLaunchKernelGGL(cc_tile_kernel, dim3((unsigned)((long long)ntx * nty)), dim3(256), 0, st, mask, H, W, ntx, connectivity == 8, labels, counters);
+    hipLaunchKernelGGL(cc_tile_kernel<K>, dim3((unsigned)((long long)ntx * nty)), dim3(256), 0, st, mask, H, W, ntx, connectivity == 8, labels, counters);
     UNET_CHECK_LAUNCH();
     const long long border = (long long)(ntx - 1) * H + (long long)(nty - 1) * W;
     if (border > 0) {
-        hipLaunchKernelGGL(cc_border_kernel, dim3(ew_grid(border, 256)), dim3(256), 0, st, mask, H, W, ntx, nty, connectivity == 8, labels, counters);
+        hipLaunchKernelGGL(cc_border_kernel<K>, dim3(ew_grid(border, 256)), dim3(256), 0, st, mask, H, W, ntx, nty, connectivity == 8, labels, counters);
         UNET_CHECK_LAUNCH();
         hipLaunchKernelGGL(cc_flatten_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, st, labels, n, counters);
         UNET_CHECK_LAUNCH();
@@ -403,6 +409,14 @@ extern "C" int unet_cc_label(const uint8_t* mask, int H, int W, int connectivity
     UNET_CHECK_ARG(aligned16(labels), "cc_label: labels must be 16-byte aligned");
     UNET_CHECK_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), (hipStream_t)stream));
     return label_launches(mask, H, W, connectivity, labels, counters, (hipStream_t)stream);
+}
+
+extern "C" int unet_cc_label_keys(const uint32_t* keys, int H, int W, int32_t* labels, int32_t* counters, void* stream) {
+    UNET_CHECK_ARG(keys && labels && counters, "cc_label_keys: null pointer");
+    UNET_CHECK_ARG(shape_ok(H, W), "cc_label_keys: H, W must be positive with H * W <= 2^31 - 1 (got %d x %d)", H, W);
+    UNET_CHECK_ARG(aligned16(labels) && (((uintptr_t)keys) & 3) == 0, "cc_label_keys: labels must be 16-byte aligned, keys 4-byte aligned");
+    UNET_CHECK_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), (hipStream_t)stream));
+    return label_launches(keys, H, W, 4, labels, counters, (hipStream_t)stream);
 }
 
 extern "C" int unet_cc_sizes(const int32_t* labels, int H, int W, int32_t* sizes, void* stream) {

@@ -1737,6 +1737,133 @@ def simp_area(xy: torch.Tensor, vring: torch.Tensor, ring_start: torch.Tensor, V
     check(lib.unet_simp_area(xy.data_ptr(), vring.data_ptr(), ring_start.data_ptr(), V, R, area2.data_ptr(), _stream()), "simp_area")
 
 
+# ---------------------------------------------------------------------------------------------- instance split (csrc/instances.hip)
+
+INST_MAX_RADIUS = 255
+INST_MAX_Q = 16 * 255          # the depth in sixteenths of a pixel
+
+
+def inst_tile_shapes():
+    """((rows, columns) of the row pass's tile, (rows, columns) of the column pass's tile) of inst_distance"""
+    v = [C.c_int(0) for _ in range(4)]
+    lib.unet_inst_tile_shapes(*(C.byref(x) for x in v))
+    return (v[0].value, v[1].value), (v[2].value, v[3].value)
+
+
+def inst_partials() -> int:
+    """int64 words of the `partial` argument of the inst_* launchers: block sums of a count, zero where a block has nothing"""
+    return int(lib.unet_inst_partials())
+
+
+def _inst_int(what: str, name: str, v, lo: int, hi: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError(f"{what}: {name} must be an int in {lo}..{hi}, got {v!r}")
+    return v
+
+
+def cc_label_keys(keys: torch.Tensor, labels: torch.Tensor, counters: torch.Tensor):
+    """cc_label at 4-adjacency of an int32 [H, W] key image (equal keys = one component): the flat zones of the instance split"""
+    _pp_tensor("cc_label_keys", "keys", keys, torch.int32, keys.shape)
+    _pp_tensor("cc_label_keys", "labels", labels, torch.int32, keys.shape)
+    _pp_tensor("cc_label_keys", "counters", counters, torch.int32, numel=4)
+    H, W = keys.shape
+    check(lib.unet_cc_label_keys(keys.data_ptr(), H, W, labels.data_ptr(), counters.data_ptr(), _stream()), "cc_label_keys")
+
+
+def inst_distance(mask: torch.Tensor, classes, radius: int, g: torch.Tensor, keys: torch.Tensor):
+    """keys [H, W] int32 = class << 16 | h, h the capped squared distance to the nearest pixel of another value for the classes in
+    `classes` and 0 for the others; g [H, W] uint8 is the workspace of the row pass"""
+    _pp_tensor("inst_distance", "mask", mask, torch.uint8, mask.shape)
+    _pp_tensor("inst_distance", "g", g, torch.uint8, mask.shape)
+    _pp_tensor("inst_distance", "keys", keys, torch.int32, mask.shape)
+    _inst_int("inst_distance", "radius", radius, 1, INST_MAX_RADIUS)
+    H, W = mask.shape
+    words = (C.c_uint32 * 8)(*vec_exclude_words(classes))
+    check(lib.unet_inst_distance(mask.data_ptr(), H, W, words, radius, g.data_ptr(), keys.data_ptr(), _stream()), "inst_distance")
+
+
+def inst_check_labels(mask: torch.Tensor, labels: torch.Tensor, bad: torch.Tensor):
+    """bad[0] = 1 unless every labels[p] names a pixel at or before p that names itself and has p's class (read it with vec_read)"""
+    _pp_tensor("inst_check_labels", "mask", mask, torch.uint8, mask.shape)
+    _pp_tensor("inst_check_labels", "labels", labels, torch.int32, mask.shape)
+    _pp_tensor("inst_check_labels", "bad", bad, torch.int64, numel=1)
+    H, W = mask.shape
+    check(lib.unet_inst_check_labels(mask.data_ptr(), labels.data_ptr(), H, W, bad.data_ptr(), _stream()), "inst_check_labels")
+
+
+def inst_ascent(keys: torch.Tensor, zone: torch.Tensor, zkey: torch.Tensor, ptr: torch.Tensor, partial: torch.Tensor):
+    """ptr[Z] at every zone root Z = the zone of the highest pixel above Z that touches it, or Z (a seed); partial sums to the seeds"""
+    _pp_tensor("inst_ascent", "keys", keys, torch.int32, keys.shape)
+    _pp_tensor("inst_ascent", "zone", zone, torch.int32, keys.shape)
+    _pp_tensor("inst_ascent", "zkey", zkey, torch.int64, keys.shape)
+    _pp_tensor("inst_ascent", "ptr", ptr, torch.int32, keys.shape)
+    _pp_tensor("inst_ascent", "partial", partial, torch.int64, numel=inst_partials())
+    H, W = keys.shape
+    check(lib.unet_inst_ascent(keys.data_ptr(), zone.data_ptr(), H, W, zkey.data_ptr(), ptr.data_ptr(), partial.data_ptr(), _stream()), "inst_ascent")
+
+
+def inst_ptr_rounds(root: torch.Tensor, a: torch.Tensor, b: torch.Tensor, rounds: int, changed: torch.Tensor):
+    """`rounds` doubling rounds of the pointers at the roots of `root` between a and b; the result is in b after an odd count"""
+    _pp_tensor("inst_ptr_rounds", "root", root, torch.int32, root.shape)
+    _pp_tensor("inst_ptr_rounds", "a", a, torch.int32, root.shape)
+    _pp_tensor("inst_ptr_rounds", "b", b, torch.int32, root.shape)
+    _inst_int("inst_ptr_rounds", "rounds", rounds, 0, 64)
+    _pp_tensor("inst_ptr_rounds", "changed", changed, torch.int32, numel=max(rounds, 1))
+    check(lib.unet_inst_ptr_rounds(root.data_ptr(), root.numel(), a.data_ptr(), b.data_ptr(), rounds, changed.data_ptr(), _stream()), "inst_ptr_rounds")
+
+
+def inst_gather(root: torch.Tensor, ptr: torch.Tensor, out: torch.Tensor):
+    """out[p] = ptr[root[p]]; out may be root"""
+    _pp_tensor("inst_gather", "root", root, torch.int32, root.shape)
+    _pp_tensor("inst_gather", "ptr", ptr, torch.int32, root.shape)
+    _pp_tensor("inst_gather", "out", out, torch.int32, root.shape)
+    check(lib.unet_inst_gather(root.data_ptr(), ptr.data_ptr(), root.numel(), out.data_ptr(), _stream()), "inst_gather")
+
+
+def inst_merge_round(keys: torch.Tensor, seg: torch.Tensor, q: int, doublings: int, peak: torch.Tensor, best: torch.Tensor, a: torch.Tensor,
+                     b: torch.Tensor, changed: torch.Tensor, partial: torch.Tensor):
+    """one merge round on seg, in place (unet_hip.h); partial sums to the segments that merged"""
+    _pp_tensor("inst_merge_round", "keys", keys, torch.int32, keys.shape)
+    for name, t in (("seg", seg), ("peak", peak), ("a", a), ("b", b)):
+        _pp_tensor("inst_merge_round", name, t, torch.int32, keys.shape)
+    _pp_tensor("inst_merge_round", "best", best, torch.int64, keys.shape)
+    _pp_tensor("inst_merge_round", "partial", partial, torch.int64, numel=inst_partials())
+    _pp_tensor("inst_merge_round", "changed", changed, torch.int32, numel=32)
+    _inst_int("inst_merge_round", "q", q, 0, INST_MAX_Q)
+    _inst_int("inst_merge_round", "doublings", doublings, 1, 32)
+    H, W = keys.shape
+    check(lib.unet_inst_merge_round(keys.data_ptr(), seg.data_ptr(), H, W, q, doublings, peak.data_ptr(), best.data_ptr(), a.data_ptr(), b.data_ptr(),
+                                    changed.data_ptr(), partial.data_ptr(), _stream()), "inst_merge_round")
+
+
+def inst_canonical(seg: torch.Tensor, lowest: torch.Tensor, labels: torch.Tensor, partial: torch.Tensor):
+    """labels[p] = the smallest linear index of p's segment; partial sums to the segments"""
+    _pp_tensor("inst_canonical", "seg", seg, torch.int32, seg.shape)
+    _pp_tensor("inst_canonical", "lowest", lowest, torch.int32, seg.shape)
+    _pp_tensor("inst_canonical", "labels", labels, torch.int32, seg.shape)
+    _pp_tensor("inst_canonical", "partial", partial, torch.int64, numel=inst_partials())
+    check(lib.unet_inst_canonical(seg.data_ptr(), seg.numel(), lowest.data_ptr(), labels.data_ptr(), partial.data_ptr(), _stream()), "inst_canonical")
+
+
+def inst_marks(mask: torch.Tensor, labels: torch.Tensor, classes, mark: torch.Tensor):
+    """mark [H, W] uint8 = 1 at the root pixel (labels[p] == p) of every segment of a class in `classes`"""
+    _pp_tensor("inst_marks", "mask", mask, torch.uint8, mask.shape)
+    _pp_tensor("inst_marks", "labels", labels, torch.int32, mask.shape)
+    _pp_tensor("inst_marks", "mark", mark, torch.uint8, mask.shape)
+    words = (C.c_uint32 * 8)(*vec_exclude_words(classes))
+    check(lib.unet_inst_marks(mask.data_ptr(), labels.data_ptr(), mask.numel(), words, mark.data_ptr(), _stream()), "inst_marks")
+
+
+def inst_ids(mask: torch.Tensor, labels: torch.Tensor, offs: torch.Tensor, classes, ids: torch.Tensor):
+    """ids [H, W] int32 (read as uint32) = offs[labels[p]] + 1 for the classes in `classes`, 0 for the others"""
+    _pp_tensor("inst_ids", "mask", mask, torch.uint8, mask.shape)
+    _pp_tensor("inst_ids", "labels", labels, torch.int32, mask.shape)
+    _pp_tensor("inst_ids", "offs", offs, torch.int32, mask.shape)
+    _pp_tensor("inst_ids", "ids", ids, torch.int32, mask.shape)
+    words = (C.c_uint32 * 8)(*vec_exclude_words(classes))
+    check(lib.unet_inst_ids(mask.data_ptr(), labels.data_ptr(), offs.data_ptr(), mask.numel(), words, ids.data_ptr(), _stream()), "inst_ids")
+
+
 # ---------------------------------------------------------------------------------------------- GeoTIFF strips on the device (csrc/tiff_encode.hip)
 
 def tiff_lzw_cap(n: int) -> int:

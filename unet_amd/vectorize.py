@@ -2,7 +2,8 @@
 tests/vectorize_ref.py restates every rule below in plain Python; the device arrays equal it bit for bit.
 
 polygonize(mask) labels the 4-connected components (label_components), traces the rings of every component and returns them as
-Polygons: only the corner vertices leave the device.  Connectivity 8 is out of scope: its components pinch at vertices and its holes
+Polygons: only the corner vertices leave the device.  polygonize_labels(mask, image) traces the segments of a label image instead (the
+instances of unet_amd/instances.py): wherever the rules below say component or label_components, read segment and that image.  Connectivity 8 is out of scope: its components pinch at vertices and its holes
 would need a point-in-polygon assignment.
 
 Vertices    pixel corners (x, y), 0 <= x <= W, 0 <= y <= H, y down; pixel (y, x) covers [x, x + 1] x [y, y + 1].
@@ -289,15 +290,23 @@ def _simplify(st: _Stages, q: int, m, labels, flags, offs, corner, ring, steps, 
                     pixels[exterior], torch.cat([tail(0), torch.cumsum(rings_of, 0)]), newring[order[stays]].to(i64), E, raw, C, rounds)
 
 
-def _polygonize(m: torch.Tensor, exclude: tuple, stages: Optional[dict] = None, q: Optional[int] = None) -> Polygons:
+def _polygonize(m: torch.Tensor, exclude: tuple, stages: Optional[dict] = None, q: Optional[int] = None,
+                given: Optional[torch.Tensor] = None) -> Polygons:
     st = _Stages(stages)
     dev = m.device
     H, W = m.shape
     n = H * W
     i32, i64, u8 = torch.int32, torch.int64, torch.uint8
-    labels, counters = _alloc((H, W), i32, dev), _alloc((4,), i32, dev)
-    ops.cc_label(m, 4, labels, counters)
-    ops.postprocess_counters(counters)
+    if given is None:
+        labels, counters = _alloc((H, W), i32, dev), _alloc((4,), i32, dev)
+        ops.cc_label(m, 4, labels, counters)
+        ops.postprocess_counters(counters)
+    else:
+        labels, bad = given, _alloc((1,), i64, dev)
+        ops.inst_check_labels(m, labels, bad)
+        if ops.vec_read(bad, 0, 1)[0]:          # a host read
+            raise ValueError("polygonize_labels: labels must name, for every pixel, a pixel of the same class at or before it that names itself "
+                             "(the smallest linear index of its segment)")
     st.mark("label")
     flags, offs = _alloc((H, W), u8, dev), _alloc((H, W), i32, dev)
     ops.vec_flags(m, labels, exclude, flags)
@@ -368,6 +377,16 @@ def _polygonize(m: torch.Tensor, exclude: tuple, stages: Optional[dict] = None, 
                     poly_ring_start, order, E)
 
 
+def check_labels(labels, m: torch.Tensor) -> torch.Tensor:
+    """the labels argument of polygonize_labels: a contiguous int32 device tensor of the mask's shape on the mask's device"""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or not labels.is_cuda:
+        raise ValueError(f"labels must be an int32 [H, W] device tensor, got {getattr(labels, 'dtype', type(labels).__name__)} on "
+                         f"{getattr(labels, 'device', 'the host')}")
+    if tuple(labels.shape) != tuple(m.shape) or labels.device != m.device:
+        raise ValueError(f"labels has shape {tuple(labels.shape)} on {labels.device}, the mask {tuple(m.shape)} on {m.device}")
+    return labels.contiguous()
+
+
 def polygonize(mask, exclude=None, simplify=None, stages: Optional[dict] = None) -> Polygons:
     """Polygons (device tensors) of the 4-connected components of a contiguous uint8 [H, W] class mask (device tensor, host tensor or NumPy
     array; host input is uploaded).  exclude: None, an int or an iterable of class ids 0..255 whose components get no polygon.
@@ -380,6 +399,18 @@ def polygonize(mask, exclude=None, simplify=None, stages: Optional[dict] = None)
     q = check_simplify(simplify)
     m, _ = _to_device(mask, torch.uint8, "polygonize")
     return _polygonize(m, exclude, stages, q)
+
+
+def polygonize_labels(mask, labels, exclude=None, simplify=None, stages: Optional[dict] = None) -> Polygons:
+    """polygonize with the given label image in the place of the component labels, so that the polygons are those of its segments.  labels: an
+    int32 [H, W] device tensor of the mask's shape; every segment must be 4-connected and of one class, and its label the smallest linear
+    index of its pixels (split_instances of unet_amd/instances.py gives such an image).  The last two are checked (ValueError), the
+    connectivity is the caller's word.  Every rule of the module docstring is stated on labels, so instances of one class that touch keep
+    one common, identically simplified border.  polygonize itself keeps its arguments and launches what it launched before this existed."""
+    exclude = check_exclude(exclude)
+    q = check_simplify(simplify)
+    m, _ = _to_device(mask, torch.uint8, "polygonize_labels")
+    return _polygonize(m, exclude, stages, q, check_labels(labels, m))
 
 
 # ------------------------------------------------------------------------------------------------------------------ GeoJSON (host)
@@ -424,12 +455,13 @@ def check_geojson_args(geotransform=None, epsg=None):
         raise ValueError(f"epsg must be None or a positive int, got {epsg!r}")
 
 
-def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, codes=None, class_zero: bool = False) -> int:
+def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, codes=None, class_zero: bool = False, instance=None) -> int:
     """One FeatureCollection with one Polygon feature per component, in poly_label order: the exterior ring, then the holes, each closed by
     repeating its first point.  Coordinates are X = gt[0] + x gt[1], Y = gt[3] + y gt[5] in float64, written with repr; integer pixel
     coordinates without a geotransform.  Properties: class (the id as the raster on disk holds it: class - 1 under class_zero, where
     class 0 -- NO_Data -- gets no feature), name (codes[class], if codes are given), pixels, area (pixels |gt[1] gt[5]|).  With an EPSG code
-    the legacy "crs" member names urn:ogc:def:crs:EPSG::<code>.  Returns the number of features.  Host code."""
+    the legacy "crs" member names urn:ogc:def:crs:EPSG::<code>.  instance: None, or one id per polygon, written as the property `instance`
+    behind the others.  Returns the number of features.  Host code."""
     check_geojson_args(geotransform, epsg)
     a = _host_arrays(polys)
     gt = None if geotransform is None else tuple(float(v) for v in geotransform)
@@ -443,6 +475,9 @@ def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, co
         raise ValueError(f"codes names {len(codes)} classes, the polygons hold class {int(a['poly_class'].max())}")
     rs, prs, rings = a["ring_start"].tolist(), a["poly_ring_start"].tolist(), a["poly_rings"].tolist()
     px_area = 1.0 if gt is None else abs(gt[1] * gt[5])
+    inst = None if instance is None else (instance.cpu().numpy() if isinstance(instance, torch.Tensor) else np.asarray(instance)).tolist()
+    if inst is not None and len(inst) != len(a["poly_class"]):
+        raise ValueError(f"instance holds {len(inst)} ids for {len(a['poly_class'])} polygons")
     feats = []
     for i, (cls, pixels) in enumerate(zip(a["poly_class"].tolist(), a["poly_pixels"].tolist())):
         if class_zero and cls == 0:
@@ -452,6 +487,8 @@ def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, co
             props["name"] = str(codes[cls])
         props["pixels"] = pixels
         props["area"] = pixels * px_area
+        if inst is not None:
+            props["instance"] = int(inst[i])
         coords = ",".join("[" + ",".join(pts[rs[r]:rs[r + 1]] + pts[rs[r]:rs[r] + 1]) + "]" for r in rings[prs[i]:prs[i + 1]])
         feats.append('{"type":"Feature","properties":' + json.dumps(props) + ',"geometry":{"type":"Polygon","coordinates":[' + coords + "]}}")
     head = '{"type":"FeatureCollection",'
@@ -489,12 +526,18 @@ def check_vector(vector, vector_exclude=None, regression: bool = False, all_clas
 
 
 def vectorize_mask(mask, path, exclude=(), geotransform=None, epsg=None, codes=None, class_zero: bool = False, timing: Optional[dict] = None,
-                   simplify=None) -> Polygons:
+                   simplify=None, labels=None, ids=None) -> Polygons:
     """polygonize + write_geojson of an assembled class mask (device or host); timing gains vector_seconds / _polygons / _vertices and
-    vector_vertices_raw (the vertices before the simplification; equal to vector_vertices without one)"""
+    vector_vertices_raw (the vertices before the simplification; equal to vector_vertices without one).  labels / ids (device tensors of
+    unet_amd/instances.py: the instance labels and their dense ids per pixel): one feature per instance, with the id of its pixels as the
+    property `instance` (0 for the components of a class that is not split)"""
     t0 = time.perf_counter()
-    polys = polygonize(mask, exclude, simplify)
-    n = write_geojson(path, polys, geotransform, epsg, codes, class_zero)
+    if labels is None:
+        polys = polygonize(mask, exclude, simplify)
+        n = write_geojson(path, polys, geotransform, epsg, codes, class_zero)
+    else:
+        polys = polygonize_labels(mask, labels, exclude, simplify)
+        n = write_geojson(path, polys, geotransform, epsg, codes, class_zero, instance=ids.view(-1)[polys.poly_label.to(torch.int64)])
     if timing is not None:
         timing.update(vector_seconds=time.perf_counter() - t0, vector_polygons=n, vector_vertices=polys.n_vertices,
                       vector_vertices_raw=polys.n_vertices if simplify is None else polys.raw_vertices)
