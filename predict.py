@@ -30,24 +30,20 @@ with half their context -- count less than the same pixels seen from the middle 
 and the weight sum are accumulated on the device in the same order as the mean (``unet_mosaic_accumulate_windows_weighted``, the weighted
 slab add and finalisation), so N ranks equal 1 rank bit for bit here too.  Refused (ValueError) for ``large_file`` and per-tile outputs.
 
-And ``postprocess=`` (None | ``unet_amd.postprocess.PostProcess`` | a dict of its arguments): a majority filter and / or a small-region sieve
-of the merged class mask on the device (``unet_amd/postprocess.py``), on rank 0, on the assembled mask -- after the rows of the other ranks
-have arrived and before ``store_tif`` -- so N ranks equal 1 rank by construction.  With one rank the mask goes from the argmax to the filters
-without leaving the device.  Only for the class mask of a merged prediction (ValueError otherwise, before the model is loaded).
-
-And ``compress=`` (None | "lzw") with ``predictor=`` (1 | 2): LZW-compressed GeoTIFF outputs.  A merged prediction is encoded where the merge
-assembled it -- on the device with one rank or RCCL (``unet_amd/tiffenc.py``), so only the compressed bytes reach the host -- and by the host
-encoder of ``unet_amd/tiffio.py`` otherwise (the int8 ``large_file`` merge, gloo ranks, per-tile outputs); the file is the same either way.
-
-And ``vector_path=`` (``predict_raster``) / ``vector=True`` (``save_predictions``) with ``vector_exclude=``: the polygons of the merged class mask
-as a GeoJSON file (``unet_amd/vectorize.py``), traced on the device of the rank that assembled the mask, after ``postprocess``; with one rank the
-mask never leaves the device for it, gloo ranks upload the assembled host mask.  Only for the class mask of a merged prediction and not with
-``large_file`` (ValueError otherwise, before the model is loaded).  ``vector_simplify=`` (a tolerance in pixels) simplifies the rings on
-the device before they are written, every shared border once and identically from both sides.
+The output options beyond the reference, each described at ``predict_raster``: ``postprocess=`` (majority filter / sieve of the merged class
+mask, ``unet_amd/postprocess.py``), ``compress=`` / ``predictor=`` / ``tile=`` / ``overviews=`` (LZW GeoTIFFs, tiled and with overviews),
+``vector_path=`` / ``vector=True`` with ``vector_exclude=`` and ``vector_simplify=`` (the mask's polygons as GeoJSON, ``unet_amd/vectorize.py``) and
+``instances=`` (touching objects split into instances, ``unet_amd/instances.py``).  ``check_outputs``, the first statement of both entry points,
+checks them from the arguments alone (ValueError before the model is loaded) into one ``OutputPlan``.  ``_write_outputs`` is the one output stage,
+on rank 0 and on the assembled mask, so N ranks equal 1 rank by construction: instances, the vector file, the raster.  The plan keeps the merged
+array where the merge assembled it while a stage needs it there: with one rank the mask goes from the argmax through the filters, the split and
+the polygonizer into the LZW encoder (``unet_amd/tiffenc.py``) on the device; the int8 ``large_file`` merge, gloo ranks and per-tile outputs use
+the host encoder of ``unet_amd/tiffio.py``: the same file.
 """
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import os
 import queue
 import threading
@@ -62,12 +58,12 @@ import torch
 from unet_amd import ops
 from unet_amd.feed import BatchFeeder, default_workers, torch_samples
 from unet_amd.learner import load_learner, open_tile
-from unet_amd.postprocess import check_postprocess
+from unet_amd.postprocess import PostProcess, check_postprocess
 from unet_amd.mosaic import MergePlan, blend_profile, check_blend, keep_windows, merge_order, sliding_windows
 from unet_amd.tiffio import check_compress, check_tiling, read_tiff, resolve_overviews, tiff_info, write_tiff
 from unet_amd.tta import parse as tta_codes
 from unet_amd.vectorize import check_vector, epsg_of_tags, vectorize_mask
-from unet_amd.instances import check_instances
+from unet_amd.instances import Instances, check_instances
 
 
 def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_zero=False, compress=None, predictor=1,
@@ -95,19 +91,97 @@ def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_ze
         timing.update(write_seconds=time.perf_counter() - t0, file_bytes=os.path.getsize(output_file))
 
 
-def _run_instances(inst, out, dev, path, geotrans, tags, compress, predictor, tile, timing):
-    """the instance split of the assembled class mask `out` (a tensor, on the device or the host) -> (the mask on the device, labels, ids);
-    path: None, or the uint32 GeoTIFF of the dense ids (0 off the split classes) with the mask's geo tags, written by tiffio.write_tiff, so
-    compress="lzw", predictor=2 and tile= apply to it as to the mask"""
-    m = torch.as_tensor(out)
-    m = (m if m.is_cuda else m.to(dev)).contiguous()
-    labels, ids, _ = inst.run(m, timing)
-    if path is not None:
-        t0 = time.perf_counter()
-        write_tiff(path, ids.cpu().numpy().view(np.uint32), geotransform=geotrans, tags=tags, compress=compress, predictor=predictor, tile=tile)
-        if timing is not None:
-            timing.update(instances_write_seconds=time.perf_counter() - t0, instances_file_bytes=os.path.getsize(path))
-    return m, labels, ids
+@dataclasses.dataclass(frozen=True)
+class OutputPlan:
+    """The output arguments of predict_raster / save_predictions as check_outputs resolved them, before the model is loaded or anything touches
+    the GPU.  Nothing downstream decides about the outputs itself: every derived value is a property (of p, the plan), stated here only."""
+    regression: bool = False
+    all_classes: bool = False
+    specific_class: Optional[int] = None
+    large_file: bool = False
+    merge: bool = True
+    class_zero: bool = False
+    raster: bool = True                               # the prediction is written as a GeoTIFF (False: predict_raster without out_path)
+    blend: str = "mean"
+    postprocess: Optional[PostProcess] = None
+    compress: Optional[str] = None
+    predictor: int = 1
+    tile: Optional[int] = None
+    overviews: Optional[str] = None                   # "mode" | "average" | "nearest": "auto" is resolved
+    vector: Optional[tuple] = None                    # the classes that get no polygon; None: no vector file
+    vector_simplify: Optional[float] = None
+    instances: Optional[Instances] = None
+    instances_raster: bool = False
+
+    mask = property(lambda p: not (p.regression or p.all_classes or p.specific_class is not None))       # the output is the class mask
+    want = property(lambda p: 0 if p.regression else "all" if p.all_classes else "argmax" if p.mask else int(p.specific_class))    # _Merge.finish
+    floats = property(lambda p: p.regression or not (p.mask or p.large_file))       # no Predictor 2, no "mode" overviews (large_file: int8 planes)
+    int8_merge = property(lambda p: p.large_file and not p.regression)
+    nodata = property(lambda p: -9999 if p.regression else None)
+    # a compressed raster is written from the tensor the merge assembled: on the device with one rank or RCCL, where only the bytes reach the host
+    encode_in_place = property(lambda p: p.compress is not None and p.raster)
+    keep = property(lambda p: p.encode_in_place or p.vector is not None or p.instances is not None)       # the merged array stays a tensor there
+
+    def needs_mask(self, subject: str, done: str, one_device: bool = True):
+        """the rule of every option that works on the class mask of a merged prediction"""
+        if not self.mask:
+            raise ValueError(f"{subject} needs the class mask: not with regression, all_classes or specific_class")
+        if one_device and self.large_file:
+            raise ValueError(f"{subject} needs the class mask on one device: not with large_file")
+        if not self.merge:
+            raise ValueError(f"{subject} needs merge=True: per-tile outputs are not {done}")
+
+
+def check_outputs(regression=False, all_classes=False, specific_class=None, large_file=False, merge=True, class_zero=False, blend="mean",
+                  postprocess=None, compress=None, predictor=1, tile=None, overviews=None, vector=None, vector_exclude=None, vector_simplify=None,
+                  instances=None, instances_raster=False, raster=True, return_array=True, raster_arg="instances_raster") -> OutputPlan:
+    """Every check of the two entry points' output arguments, from the arguments alone and in one order -> the OutputPlan.  vector: vector= or
+    vector_path=; instances_raster: whether the argument named raster_arg asks for the instance raster; raster: whether out_path is given"""
+    mode = OutputPlan(bool(regression), bool(all_classes), specific_class, bool(large_file), bool(merge), bool(class_zero), bool(raster))
+    check_blend(blend, large_file, merge)
+    post = check_postprocess(postprocess)
+    if post is not None:
+        mode.needs_mask("postprocess", "post-processed", one_device=False)       # the mask of the int8 merge is uploaded for it
+    compress, predictor = check_compress(compress, predictor, mode.floats)
+    tile, overviews = check_tiling(compress, tile, overviews, auto=True)
+    tile, overviews = check_tiling(compress, tile, resolve_overviews(overviews, mode.mask), mode.floats)
+    vec = check_vector(vector, vector_exclude, class_zero, vector_simplify)
+    if vec is not None:
+        mode.needs_mask("a vector output", "polygonized")
+    if instances is None and instances_raster:
+        raise ValueError(f"{raster_arg} without instances")
+    inst = check_instances(instances)
+    if inst is not None:
+        mode.needs_mask("instances", "split")
+        if vec is None and not instances_raster:
+            raise ValueError("instances without an output: ask for the vector file, the instance raster or both")
+    if not return_array and not raster and vec is None:
+        raise ValueError("return_array=False needs out_path: the prediction would go nowhere")
+    return dataclasses.replace(mode, blend=blend, postprocess=post, compress=compress, predictor=predictor, tile=tile, overviews=overviews,
+                               vector=vec, vector_simplify=vector_simplify, instances=inst, instances_raster=bool(instances_raster))
+
+
+def _write_outputs(plan: OutputPlan, out, device, gt, tags, raster_path, vector_path, instances_path, class_names, timing):
+    """Rank 0's output stage on the merged array `out` of _Merge.finish (a tensor under plan.keep, else a NumPy array): the instance split (its
+    dense ids as a uint32 GeoTIFF with the mask's geo tags, by tiffio.write_tiff, so compress, predictor and tile apply to it as to the mask),
+    the vector file, the move to the host unless the raster is encoded from the tensor, the raster.  Returns what the raster is written from."""
+    labels = ids = None
+    if plan.instances is not None:
+        out = torch.as_tensor(out)
+        out = (out if out.is_cuda else out.to(device)).contiguous()
+        labels, ids, _ = plan.instances.run(out, timing)
+        if instances_path is not None:
+            t0 = time.perf_counter()
+            write_tiff(instances_path, ids.cpu().numpy().view(np.uint32), gt, tags, compress=plan.compress, predictor=plan.predictor, tile=plan.tile)
+            if timing is not None:
+                timing.update(instances_write_seconds=time.perf_counter() - t0, instances_file_bytes=os.path.getsize(instances_path))
+    if plan.vector is not None:
+        vectorize_mask(out, vector_path, plan.vector, gt, epsg_of_tags(tags), class_names, plan.class_zero, timing, plan.vector_simplify, labels, ids)
+    if not plan.encode_in_place and isinstance(out, torch.Tensor):
+        out = out.cpu().numpy()
+    if raster_path is not None:
+        store_tif(raster_path, out, gt, tags, plan.nodata, plan.class_zero, plan.compress, plan.predictor, timing, plan.tile, plan.overviews)
+    return out
 
 
 def _geo(path):
@@ -151,8 +225,7 @@ class _Merge:
     """Runs one rank's share of a merged prediction: forward of its placements in batches, accumulation into its strip of the
     mosaic, slab exchange with the neighbours, finalisation, gather of the requested output on rank 0."""
 
-    def __init__(self, model, places: np.ndarray, MH: int, MW: int, regression: bool, int8_merge: bool, rank: int, world: int,
-                 blend: str = "mean"):
+    def __init__(self, model, places: np.ndarray, MH: int, MW: int, regression: bool, int8_merge: bool, rank: int, world: int, blend: str = "mean"):
         self.model, self.dev = model, model._device
         self.C = model.n_out
         self.raw, self.int8 = bool(regression), bool(int8_merge)
@@ -253,9 +326,8 @@ class _Merge:
 
     def finish(self, want, postprocess=None, timing: Optional[dict] = None, keep: bool = False):
         """want: "argmax" | "all" | int class index.  Returns (on rank 0) the full-size numpy array, None elsewhere.  postprocess: a
-        PostProcess applied to the assembled class mask on rank 0 (want == "argmax" only: check_postprocess).  keep: the result stays
-        where it was assembled and comes back as a tensor -- on the device with one rank or RCCL, on the host for the int8 merge and
-        gloo -- for store_tif to encode it there"""
+        PostProcess applied to the assembled class mask on rank 0 (want == "argmax" only: check_outputs).  keep (OutputPlan.keep): the result
+        comes back as the tensor it was assembled in -- on the device with one rank or RCCL, on the host for the int8 merge and gloo"""
         rows, MW, MH = self.hi - self.lo, self.plan.MW, self.plan.MH
         if self.int8:
             merged, counter = self.mosaic[:, :rows].cpu().numpy(), self.count[:, :rows].cpu().numpy()
@@ -270,9 +342,8 @@ class _Merge:
             elif rows > 0:
                 ops.mosaic_finalize_rows_weighted(self.mosaic, self.count, self.wsum, 0, rows, am, fill=-9999.0 if self.raw else None)
             part = am[:rows] if want == "argmax" else (self.mosaic[:, :rows] if want == "all" else self.mosaic[want, :rows])
-        gather = (lambda p, planes: self._gather_rows(p, planes, True)) if keep else self._gather_rows
         if postprocess is None:
-            return gather(part, want == "all")
+            return self._gather_rows(part, want == "all", True) if keep else self._gather_rows(part, want == "all")
         # one rank: the mask goes from the argmax to the filters on the device; N ranks: rank 0 uploads the assembled mask again
         full = part if self.world == 1 else self._gather_rows(part, False)
         if full is None:
@@ -315,8 +386,7 @@ def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch
                tta: Optional[Tuple[int, ...]] = None, blend: str = "mean", postprocess=None, keep: bool = False):
     """make_input(first, n, n_pad) -> ops.WindowBatch of placements [first, first + n) padded to n_pad windows (so that every
     forward runs on ONE batch geometry and no second set of activation buffers is allocated).  tta: parsed codes -- every batch runs
-    len(tta) forwards of that same geometry and the averaged probabilities take the place of the softmax in the merge.  blend: "mean" |
-    "gaussian" (unet_amd/mosaic.py).  postprocess: a checked PostProcess or None.  keep: _Merge.finish"""
+    len(tta) forwards of that same geometry, their mean takes the place of the softmax in the merge.  The rest: OutputPlan's values"""
     mg = _Merge(model, places, MH, MW, regression, int8_merge, rank, world, blend)
     t0 = time.perf_counter()
     batches = mg.plan.batches(rank, batch)
@@ -344,33 +414,6 @@ def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch
 def _dist_ctx():
     from unet_amd.distributed import init_from_env
     return init_from_env()
-
-
-def _float_output(regression, all_classes, specific_class, large_file) -> bool:
-    """whether the output holds float samples (which Predictor 2 does not take): known from the arguments, before the model is loaded"""
-    return bool(regression or ((all_classes or specific_class is not None) and not large_file))
-
-
-def _overviews(overviews, regression, all_classes, specific_class, large_file):
-    """ "auto" -> "mode" for a class mask, "average" for everything else: float probabilities, regression, and the probabilities that
-    large_file stretches into int8 planes"""
-    stretched = bool(large_file and (all_classes or specific_class is not None))
-    return resolve_overviews(overviews, not _float_output(regression, all_classes, specific_class, large_file) and not stretched)
-
-
-def _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file):
-    """tile= / overviews= of the prediction entry points, from the arguments alone -> (tile, resampling of the overviews or None)"""
-    tile, overviews = check_tiling(compress, tile, overviews, auto=True)
-    overviews = _overviews(overviews, regression, all_classes, specific_class, large_file)
-    return check_tiling(compress, tile, overviews, _float_output(regression, all_classes, specific_class, large_file))
-
-
-def _want(regression, all_classes, specific_class):
-    if regression:
-        return 0                                      # the single band
-    if all_classes:
-        return "all"
-    return "argmax" if specific_class is None else int(specific_class)
 
 
 # ----------------------------------------------------------------------------------------------- configs[4]: a whole raster
@@ -464,16 +507,9 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
-    check_blend(blend, large_file)
-    post = check_postprocess(postprocess, regression, all_classes, specific_class)
-    check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
-    tile, overviews = _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file)
-    vec = check_vector(vector_path, vector_exclude, regression, all_classes, specific_class, large_file, True, class_zero, vector_simplify)
-    if instances is None and instances_path is not None:
-        raise ValueError("instances_path without instances")
-    inst = check_instances(instances, regression, all_classes, specific_class, large_file, True, vec is not None or instances_path is not None)
-    if not return_array and out_path is None and vec is None:
-        raise ValueError("return_array=False needs out_path: the prediction would go nowhere")
+    plan = check_outputs(regression, all_classes, specific_class, large_file, True, class_zero, blend, postprocess, compress, predictor, tile,
+                         overviews, vector_path, vector_exclude, vector_simplify, instances, instances_raster=instances_path is not None,
+                         raster=out_path is not None, return_array=return_array, raster_arg="instances_path")
     model = getattr(model, "model", model)
     codes = tta_codes(tta, [(size, size)])
     rank, _, world = _dist_ctx()
@@ -512,22 +548,12 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
         _check_batch(first, n, n_pad, len(rows))
         return ops.WindowBatch(src, gtab, first, n_pad, size, size)
 
-    want = _want(regression, all_classes, specific_class)
-    keep_out = compress is not None and out_path is not None          # the encoder takes the array where the merge assembled it
     with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
-        out = _run_merge(model, places, MH, MW, regression, bool(large_file and not regression), rank, world, batch_size, make_input, want, timing,
-                         codes, blend, post, keep_out or vec is not None or inst is not None)
-    ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
-    labels = ids = None
-    if rank == 0 and inst is not None:
-        out, labels, ids = _run_instances(inst, out, dev, instances_path, ogt, tags, compress, predictor, tile, timing)
-    if rank == 0 and vec is not None:
-        vectorize_mask(out, vector_path, vec, ogt, epsg_of_tags(tags), None, class_zero, timing, vector_simplify, labels, ids)
-    if rank == 0 and (vec is not None or inst is not None):
-        if not keep_out and isinstance(out, torch.Tensor):
-            out = out.cpu().numpy()
-    if rank == 0 and out_path is not None:
-        store_tif(out_path, out, ogt, tags, -9999 if regression else None, class_zero, compress, predictor, timing, tile, overviews)
+        out = _run_merge(model, places, MH, MW, plan.regression, plan.int8_merge, rank, world, batch_size, make_input, plan.want, timing, codes,
+                         plan.blend, plan.postprocess, plan.keep)
+    if rank == 0:
+        ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
+        out = _write_outputs(plan, out, dev, ogt, tags, out_path, vector_path, instances_path, None, timing)
     if timing is not None:
         timing.update(kept_windows=len(wins), all_windows=int(len(keep)), mosaic=(MH, MW))
     if rank != 0 or not return_array:
@@ -688,30 +714,17 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
                      batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
                      tile=None, overviews=None, vector: bool = False, vector_exclude=None, vector_simplify=None, instances=None,
                      instances_raster: bool = False):
-    """tta: None | "flips" | "d4" | a tuple of D4 codes (see predict_raster and unet_amd/tta.py), merged and per-tile outputs alike.
-    blend: "mean" | "gaussian" (see predict_raster): how the windows of a merged prediction combine; only with merge=True (per-tile
-    outputs have no overlap) and not with large_file (ValueError before the model is loaded).
-    postprocess: None | PostProcess | dict of its arguments (see predict_raster): only with merge=True and for the class mask (ValueError
-    before the model is loaded).
-    compress / predictor: None | "lzw", 1 | 2 (see predict_raster).  The merged raster is encoded where the merge assembled it (on the
-    device with one rank or RCCL); per-tile outputs (merge=False) use the host encoder.
-    tile / overviews (see predict_raster): tiles and the overview pyramid of the MERGED raster only; per-tile outputs (merge=False) ignore
-    them, as a tile is one block anyway.
-    vector / vector_exclude (see predict_raster's vector_path): True writes <merged raster stem>.geojson beside the merged raster, with the
-    class names of the model's vocab; only with merge=True, for the class mask and not with large_file (ValueError before the model is loaded).
-    vector_simplify: None | a tolerance in pixels (see predict_raster); needs vector=True.
-    instances / instances_raster (see predict_raster's instances / instances_path): the instance split of the merged class mask; True writes
-    <merged raster stem>_instances.tif beside the merged raster.  Needs merge=True and vector=True, instances_raster=True or both
-    (ValueError before the model is loaded).
+    """tta, blend, postprocess, compress / predictor, tile / overviews, vector_exclude, vector_simplify and instances are predict_raster's (see
+    there); the ValueErrors of check_outputs come before the model is loaded.  What differs here: tta applies to merged and per-tile outputs
+    alike; blend, postprocess, vector and instances need merge=True (per-tile outputs: no overlap to blend, not post-processed, polygonized, split).
+    compress / predictor: the merged raster is encoded where the merge assembled it (on the device with one rank or RCCL); per-tile outputs
+    (merge=False) use the host encoder.  tile / overviews: of the MERGED raster only; per-tile outputs ignore them, as a tile is one block anyway.
+    vector (predict_raster's vector_path): True writes <merged raster stem>.geojson beside the merged raster, with the class names of the
+    model's vocab.  instances_raster (predict_raster's instances_path): True writes <merged raster stem>_instances.tif beside it; instances
+    needs vector=True, instances_raster=True or both.
     validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
-    check_blend(blend, large_file, merge)
-    post = check_postprocess(postprocess, regression, all_classes, specific_class, merge)
-    check_compress(compress, predictor, _float_output(regression, all_classes, specific_class, large_file))
-    tile, overviews = _check_tiling(compress, tile, overviews, regression, all_classes, specific_class, large_file)
-    vec = check_vector(vector or None, vector_exclude, regression, all_classes, specific_class, large_file, merge, class_zero, vector_simplify)
-    if instances is None and instances_raster:
-        raise ValueError("instances_raster without instances")
-    inst = check_instances(instances, regression, all_classes, specific_class, large_file, merge, vec is not None or bool(instances_raster))
+    plan = check_outputs(regression, all_classes, specific_class, large_file, merge, class_zero, blend, postprocess, compress, predictor, tile,
+                         overviews, vector or None, vector_exclude, vector_simplify, instances, instances_raster)
     rank, local_rank, world = _dist_ctx()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model
@@ -728,12 +741,9 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     t_start = time.perf_counter()
     windows = _tile_windows(batch_size, model._device, learn.dls.train_ds.dtype == "int16")
     if merge:
-        out, gt = _save_merged(model, tiles, geos, windows, rank, world, regression, _want(regression, all_classes, specific_class),
-                               bool(large_file and not regression), batch_size, batch_invariant, codes, blend, timing, post,
-                               compress is not None or vec is not None or inst is not None)
+        out, gt = _save_merged(model, tiles, geos, windows, rank, world, plan, batch_size, batch_invariant, codes, timing)
     else:
-        _save_tiles(model, tiles, geos, windows, rank, world, output_folder, regression, all_classes, specific_class, large_file, class_zero,
-                    batch_size, batch_invariant, codes, compress, predictor)
+        _save_tiles(model, tiles, geos, windows, rank, world, output_folder, plan, batch_size, batch_invariant, codes)
         if world > 1:
             _dist().barrier()
     if timing is not None:
@@ -745,25 +755,15 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     if rank != 0:
         return None
     name = "_".join(filter(None, [AOI, year, model_name, "prediction"])) + ".tif"
-    labels = ids = None
-    if inst is not None:
-        ipath = output_folder / (Path(name).stem + "_instances.tif") if instances_raster else None
-        out, labels, ids = _run_instances(inst, out, model._device, ipath, gt, geos[0][1], compress, predictor, tile, timing)
-    if vec is not None:
-        vocab = getattr(learn.dls, "vocab", None)
-        names = list(vocab) if vocab is not None and len(vocab) >= model.n_out else None
-        vectorize_mask(out, (output_folder / name).with_suffix(".geojson"), vec, gt, epsg_of_tags(geos[0][1]), names, class_zero, timing, vector_simplify,
-                       labels, ids)
-    if vec is not None or inst is not None:
-        if compress is None and isinstance(out, torch.Tensor):
-            out = out.cpu().numpy()
-    store_tif(output_folder / name, out, gt, geos[0][1], -9999 if regression else None, class_zero, compress, predictor, timing, tile, overviews)
+    vocab = getattr(learn.dls, "vocab", None) if plan.vector is not None else None
+    names = list(vocab) if vocab is not None and len(vocab) >= model.n_out else None
+    _write_outputs(plan, out, model._device, gt, geos[0][1], output_folder / name, (output_folder / name).with_suffix(".geojson"),
+                   output_folder / (Path(name).stem + "_instances.tif") if plan.instances_raster else None, names, timing)
     print(f"Prediction stored in {output_folder}.")
     return output_folder if regression else output_folder / name
 
 
-def _save_merged(model, tiles, geos, windows: Callable, rank, world, regression, want, int8_merge, batch_size, batch_invariant, codes, blend,
-                 timing, postprocess=None, keep: bool = False):
+def _save_merged(model, tiles, geos, windows: Callable, rank, world, plan: OutputPlan, batch_size, batch_invariant, codes, timing):
     """overlap merge (predict.py:257-355) of this rank's share of the tiles -> (merged array on rank 0, None elsewhere; geotransform of
     the mosaic).  The extent follows from the tiles' geotransforms and sizes, which are known from the headers BEFORE any tile is
     predicted: every batch is accumulated into the device mosaic as soon as it is computed and its probabilities are dropped (the
@@ -780,15 +780,15 @@ def _save_merged(model, tiles, geos, windows: Callable, rank, world, regression,
         warnings.warn("Not all tiles have the same resolution.")
     MW, MH = round((lrx_full - ulx_full) / xres), round((lry_full - uly_full) / yres)
     if rank == 0:
-        print(f"True merged raster size: {model.n_out * MH * MW * (1 if int8_merge else 4) / (1024 ** 2): .1f}MB.")
+        print(f"True merged raster size: {model.n_out * MH * MW * (1 if plan.int8_merge else 4) / (1024 ** 2): .1f}MB.")
     places = np.array([[round((gts[i, 3] - uly_full) / yres), round((gts[i, 0] - ulx_full) / xres), geos[i][2], geos[i][3]]
                        for i in range(len(tiles))], dtype=np.int64)
     order = merge_order(places)
     places, tiles_o = places[order], [tiles[i] for i in order]
-    plan = MergePlan(places, MH, MW, world)
+    batches = MergePlan(places, MH, MW, world).batches(rank, batch_size)
     sizes = [(int(p_[2]), int(p_[3])) for p_ in places]
     # (the decode pool and its pinned ring live for one call)
-    with _prefetcher(tiles_o, plan.batches(rank, batch_size), sizes, model._device) as pf, contextlib.closing(iter(pf)) as feed:
+    with _prefetcher(tiles_o, batches, sizes, model._device) as pf, contextlib.closing(iter(pf)) as feed:
         def make_input(first, n, n_pad):
             pf.done()          # staging of the batch in flight: released once the NEXT batch is asked for (its gather has been issued by then)
             f, nn, d = next(feed)
@@ -796,13 +796,12 @@ def _save_merged(model, tiles, geos, windows: Callable, rank, world, regression,
             return windows(d, n)
 
         with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):          # (see predict_raster)
-            out = _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch_size, make_input, want, timing, codes, blend,
-                             postprocess, keep)
+            out = _run_merge(model, places, MH, MW, plan.regression, plan.int8_merge, rank, world, batch_size, make_input, plan.want, timing, codes,
+                         plan.blend, plan.postprocess, plan.keep)
     return out, [ulx_full, xres, 0.0, uly_full, 0.0, yres]
 
 
-def _save_tiles(model, tiles, geos, windows: Callable, rank, world, output_folder, regression, all_classes, specific_class, large_file,
-                class_zero, batch_size, batch_invariant, codes, compress=None, predictor=1):
+def _save_tiles(model, tiles, geos, windows: Callable, rank, world, output_folder, plan: OutputPlan, batch_size, batch_invariant, codes):
     """one output file per tile (predict.py:224-254); tile i -> rank i mod world"""
     dev, C = model._device, model.n_out
     mine = list(range(rank, len(tiles), world))
@@ -815,7 +814,7 @@ def _save_tiles(model, tiles, geos, windows: Callable, rank, world, output_folde
         batches.append((i, n))
         i += n
     mtiles = [tiles[i] for i in mine]
-    need_p = regression or all_classes or specific_class is not None
+    need_p = not plan.mask
     acc = None      # the TTA accumulator, used again by every batch of the same tile size (see _run_merge)
     with _prefetcher(mtiles, batches, sizes, dev) as pf:
         for first, n, d in pf:
@@ -827,11 +826,11 @@ def _save_tiles(model, tiles, geos, windows: Callable, rank, world, output_folde
                 if codes is None:
                     z = model.forward_windows(wb)
                 else:                # TTA: the finalising accumulate writes the mean probabilities (values) / their argmax
-                    acc = model.forward_tta(wb, n, codes, bool(regression), acc, probs, amax).buf
+                    acc = model.forward_tta(wb, n, codes, plan.regression, acc, probs, amax).buf
             pf.done()                  # (the gather that reads the staging buffer has been issued)
             if codes is None:
                 zs = ops.TS(z.buf[:n], z.co, z.C)
-                if regression:       # predict.py:195-197: tile_preds[1] = raw outputs [1,H,W]
+                if plan.regression:       # predict.py:195-197: tile_preds[1] = raw outputs [1,H,W]
                     ops.nhwc_to_nchw(zs, probs)
                 else:
                     ops.softmax_argmax(zs, probs, amax)
@@ -839,8 +838,8 @@ def _save_tiles(model, tiles, geos, windows: Callable, rank, world, output_folde
             for j in range(n):
                 t = mtiles[first + j]
                 gt, tags = geos[mine[first + j]][0], geos[mine[first + j]][1]
-                out = outs[j] if regression or all_classes or specific_class is None else outs[j, specific_class]
-                if large_file and out.dtype.kind == "f" and out.max() <= 1 and (all_classes or specific_class):
+                out = outs[j] if plan.regression or plan.all_classes or plan.specific_class is None else outs[j, plan.specific_class]
+                if plan.large_file and out.dtype.kind == "f" and out.max() <= 1 and (plan.all_classes or plan.specific_class):
                     out = np.around(out * LARGE_FILE_SCALE).astype(np.int8)
                 name = t.name if t.suffix != ".npy" else t.stem + ".tif"
-                store_tif(output_folder / name, out, gt, tags, None, class_zero, compress, predictor)
+                store_tif(output_folder / name, out, gt, tags, None, plan.class_zero, plan.compress, plan.predictor)

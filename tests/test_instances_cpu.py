@@ -124,7 +124,9 @@ def test_split_instances_refuses_bad_arguments_before_the_gpu():
 
 def test_check_instances():
     IN = _inst()
-    assert IN.check_instances(None, regression=True, merge=False, outputs=False) is None          # None is never refused
+    from predict import check_outputs
+    assert check_outputs(instances=None, regression=True, merge=False).instances is None          # None is never refused
+    assert IN.check_instances(None) is None
     got = IN.check_instances({"classes": [2, 1], "radius": 16})
     assert isinstance(got, IN.Instances) and (got.classes, got.radius, got.min_depth, got.max_rounds) == ((1, 2), 16, 2.0, 64)
     same = IN.Instances(2)
@@ -132,9 +134,11 @@ def test_check_instances():
     for bad in ({"classes": 1, "depth": 2}, {}, {"classes": 300}, [1], 1, "trees"):
         with pytest.raises(ValueError):
             IN.check_instances(bad)
-    for kw in (dict(regression=True), dict(all_classes=True), dict(specific_class=0), dict(large_file=True), dict(merge=False), dict(outputs=False)):
+    assert check_outputs(instances=same, instances_raster=True).instances is same
+    for kw in (dict(regression=True), dict(all_classes=True), dict(specific_class=0), dict(large_file=True), dict(merge=False),
+               dict(instances_raster=False)):          # the last: no output
         with pytest.raises(ValueError):
-            IN.check_instances(same, **kw)
+            check_outputs(**dict(dict(instances=same, instances_raster=True), **kw))
 
 
 def test_polygonize_refuses_bad_labels_before_the_gpu():

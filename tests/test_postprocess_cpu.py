@@ -78,6 +78,7 @@ def test_reference_round_counts_stay_within_the_cap():
 # ------------------------------------------------------------------------------------------------------------ argument refusals
 
 def test_postprocess_argument_errors():
+    from predict import check_outputs
     from unet_amd.postprocess import PostProcess, check_postprocess
     for bad in (dict(majority=4), dict(majority=1), dict(majority=17), dict(majority=-3), dict(majority=3.0), dict(sieve=-1), dict(sieve=2.5),
                 dict(connectivity=6), dict(max_rounds=0), dict(frozen_class=256), dict(frozen_class=-1)):
@@ -91,7 +92,7 @@ def test_postprocess_argument_errors():
     assert isinstance(q, PostProcess) and (q.majority, q.sieve, q.connectivity, q.max_rounds, q.frozen_class) == (3, 0, 4, 16, None)
     for kw in (dict(regression=True), dict(all_classes=True), dict(specific_class=2), dict(specific_class=0), dict(merge=False)):
         with pytest.raises(ValueError):
-            check_postprocess(p, **kw)
+            check_outputs(postprocess=p, **kw)
     with pytest.raises(ValueError):
         check_postprocess({"majorty": 3})
     with pytest.raises(ValueError):

@@ -269,11 +269,14 @@ def test_prediction_entry_points_refuse_bad_arguments_before_the_model_is_loaded
         regression = kw.pop("regression", False)
         with pytest.raises(ValueError, match=match):
             P.save_predictions(tmp_path / "missing.pkl", tmp_path, regression, merge=True, **kw)
-    assert P._overviews("auto", False, False, None, False) == "mode" and P._overviews("auto", False, True, None, False) == "average"
-    assert P._overviews("auto", True, False, None, False) == "average" and P._overviews("auto", False, True, None, True) == "average"
-    assert P._overviews("auto", False, False, None, True) == "mode" and P._overviews("auto", False, False, 2, False) == "average"
-    assert P._overviews("auto", False, False, 2, True) == "average"
-    assert P._overviews("nearest", False, False, None, False) == "nearest" and P._overviews(None, False, False, None, False) is None
+
+    def resolved(overviews, regression, all_classes, specific_class, large_file):
+        return P.check_outputs(regression, all_classes, specific_class, large_file, compress="lzw", tile=256, overviews=overviews).overviews
+    assert resolved("auto", False, False, None, False) == "mode" and resolved("auto", False, True, None, False) == "average"
+    assert resolved("auto", True, False, None, False) == "average" and resolved("auto", False, True, None, True) == "average"
+    assert resolved("auto", False, False, None, True) == "mode" and resolved("auto", False, False, 2, False) == "average"
+    assert resolved("auto", False, False, 2, True) == "average"
+    assert resolved("nearest", False, False, None, False) == "nearest" and resolved(None, False, False, None, False) is None
 
 
 def test_tile_and_overviews_of_params_and_main_reach_save_predictions(monkeypatch):

@@ -205,7 +205,7 @@ def test_prediction_entry_points_refuse_bad_arguments_before_the_model_is_loaded
         P.save_predictions(missing, tmp_path, True, merge=False, compress="lzw", predictor=2)
     with pytest.raises(ValueError, match="return_array"):
         P.predict_raster(None, raster, 32, return_array=False)
-    assert P._float_output(False, True, None, True) is False          # the int8 merge of large_file holds integers: Predictor 2 is fine
+    assert P.check_outputs(False, True, None, True).floats is False          # the int8 merge of large_file holds integers: Predictor 2 is fine
 
 
 def test_compress_setting_of_params_and_main_reaches_save_predictions(monkeypatch):

@@ -201,10 +201,9 @@ class Instances:
         return labels, ids, info
 
 
-def check_instances(instances, regression: bool = False, all_classes: bool = False, specific_class=None, large_file: bool = False,
-                    merge: bool = True, outputs: bool = True) -> Optional[Instances]:
-    """the instances= argument (None | Instances | dict of its arguments), validated before the model is loaded or anything touches the GPU
-    -> Instances or None.  outputs: is a vector file or an instance raster requested?"""
+def check_instances(instances) -> Optional[Instances]:
+    """the instances= argument (None | Instances | dict of its arguments) -> Instances or None; which outputs take one, and that it needs
+    somewhere to go, are predict.check_outputs' rules"""
     if instances is None:
         return None
     if isinstance(instances, dict):
@@ -214,12 +213,4 @@ def check_instances(instances, regression: bool = False, all_classes: bool = Fal
             raise ValueError(f"instances={instances!r}: {e}") from None
     if not isinstance(instances, Instances):
         raise ValueError(f"instances must be None, an Instances or a dict of its arguments, got {type(instances).__name__}")
-    if regression or all_classes or specific_class is not None:
-        raise ValueError("instances needs the class mask: not with regression, all_classes or specific_class")
-    if large_file:
-        raise ValueError("instances needs the class mask on one device: not with large_file")
-    if not merge:
-        raise ValueError("instances needs merge=True: per-tile outputs are not split")
-    if not outputs:
-        raise ValueError("instances without an output: ask for the vector file, the instance raster or both")
     return instances

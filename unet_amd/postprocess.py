@@ -190,9 +190,9 @@ class PostProcess:
         return self.run(mask)[0]
 
 
-def check_postprocess(postprocess, regression: bool = False, all_classes: bool = False, specific_class=None, merge: bool = True):
-    """the postprocess= argument of predict_raster / save_predictions (None | PostProcess | dict of its arguments), validated before the
-    model is loaded or anything touches the GPU -> PostProcess or None"""
+def check_postprocess(postprocess):
+    """the postprocess= argument of predict_raster / save_predictions (None | PostProcess | dict of its arguments) -> PostProcess or None;
+    which outputs take one is predict.check_outputs' rule"""
     if postprocess is None:
         return None
     if isinstance(postprocess, dict):
@@ -202,8 +202,4 @@ def check_postprocess(postprocess, regression: bool = False, all_classes: bool =
             raise ValueError(f"postprocess={postprocess!r}: {e}") from None
     if not isinstance(postprocess, PostProcess):
         raise ValueError(f"postprocess must be None, a PostProcess or a dict of its arguments, got {type(postprocess).__name__}")
-    if regression or all_classes or specific_class is not None:
-        raise ValueError("postprocess needs the class mask: not with regression, all_classes or specific_class")
-    if not merge:
-        raise ValueError("postprocess needs merge=True: per-tile outputs are not post-processed")
     return postprocess

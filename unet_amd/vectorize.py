@@ -501,11 +501,10 @@ def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, co
 
 # ------------------------------------------------------------------------------------------------------------------ entry points
 
-def check_vector(vector, vector_exclude=None, regression: bool = False, all_classes: bool = False, specific_class=None, large_file: bool = False,
-                 merge: bool = True, class_zero: bool = False, simplify=None) -> Optional[tuple]:
-    """the vector_path= / vector= and vector_exclude= arguments of predict_raster / save_predictions, validated before the model is loaded or
-    anything touches the GPU -> the classes to exclude (a tuple), or None when no vector file is wanted.  simplify (vector_simplify=): None or
-    a finite tolerance of 0..4096 pixels, only with a vector output"""
+def check_vector(vector, vector_exclude=None, class_zero: bool = False, simplify=None) -> Optional[tuple]:
+    """the vector_path= / vector= and vector_exclude= arguments of predict_raster / save_predictions -> the classes to exclude (a tuple), or
+    None when no vector file is wanted.  simplify (vector_simplify=): None or a finite tolerance of 0..4096 pixels, only with a vector output.
+    Which outputs can be polygonized is predict.check_outputs' rule"""
     if vector is None or vector is False:
         if vector_exclude is not None:
             raise ValueError("vector_exclude without a vector output")
@@ -514,15 +513,7 @@ def check_vector(vector, vector_exclude=None, regression: bool = False, all_clas
         return None
     check_simplify(simplify)
     exclude = check_exclude(vector_exclude)
-    if regression or all_classes or specific_class is not None:
-        raise ValueError("a vector output needs the class mask: not with regression, all_classes or specific_class")
-    if large_file:
-        raise ValueError("a vector output needs the class mask on one device: not with large_file")
-    if not merge:
-        raise ValueError("a vector output needs merge=True: per-tile outputs are not polygonized")
-    if class_zero:
-        exclude = tuple(sorted(set(exclude) | {0}))
-    return exclude
+    return tuple(sorted(set(exclude) | {0})) if class_zero else exclude
 
 
 def vectorize_mask(mask, path, exclude=(), geotransform=None, epsg=None, codes=None, class_zero: bool = False, timing: Optional[dict] = None,
