@@ -58,11 +58,28 @@ def create_train_test_split(path, split=None, seed: Optional[int] = None):
     return {k: len(v) for k, v in parts.items()}
 
 
+def is_vector_mask(path) -> bool:
+    return str(path).lower().endswith((".geojson", ".json"))
+
+
+def burn_vector_mask(path, shape, geotransform, attribute="class"):
+    """(mask, meta) in the place of read_tiff's for a GeoJSON mask: its polygons burnt on the GPU onto the grid of the image (its shape and
+    geotransform, fill 0); the mask has the image's geotransform and no nodata value.  class_zero is the caller's `mask + 1`."""
+    import torch
+    if not torch.cuda.is_available():
+        raise ValueError(f"{path}: a vector mask is burnt on the GPU and there is no device; rasterize it beforehand and pass the GeoTIFF")
+    from unet_amd.rasterize import rasterize_geojson
+    mask = rasterize_geojson(path, tuple(int(v) for v in shape), geotransform, attribute, fill=0, class_zero=False)
+    return mask.cpu().numpy(), {"geotransform": tuple(geotransform), "nodata": None, "tags": {}}
+
+
 def split_raster(path_to_raster=None, path_to_mask=None, base_dir=".", patch_size=400, patch_overlap=0.20, split=None, max_empty=0.9,
-                 class_zero=False, seed: Optional[int] = None, compress=None, predictor=1):
+                 class_zero=False, seed: Optional[int] = None, compress=None, predictor=1, mask_attribute="class"):
     """Cut a raster (and its mask) into patch_size tiles, drop tiles that are more than max_empty empty, write GeoTIFF tiles
     with their own geotransform and split them into trai / vali / test.  compress / predictor go straight to tiffio.write_tiff
-    ("lzw", 2: LZW tiles with horizontal differencing; the reader and the feed take them as they take uncompressed ones)."""
+    ("lzw", 2: LZW tiles with horizontal differencing; the reader and the feed take them as they take uncompressed ones).
+    A mask path that ends in .geojson or .json holds polygons instead of a raster: they are burnt on the GPU onto the image's grid
+    (unet_amd/rasterize.py: the pixel centre decides, fill 0) with their integer property `mask_attribute` as the class id."""
     if split is None:
         split = [0.7, 0.2, 0.1]
     base = Path(base_dir)
@@ -72,7 +89,7 @@ def split_raster(path_to_raster=None, path_to_mask=None, base_dir=".", patch_siz
     nodata = meta.get("nodata")
     mask = None
     if path_to_mask is not None:
-        mask, mmeta = read_tiff(path_to_mask)
+        mask, mmeta = burn_vector_mask(path_to_mask, img.shape[1:], gt, mask_attribute) if is_vector_mask(path_to_mask) else read_tiff(path_to_mask)
         mask = mask[None] if mask.ndim == 2 else mask
         mgt = mmeta["geotransform"] or gt
         if mask.shape[1:] != img.shape[1:] or mgt[0] != gt[0] or mgt[3] != gt[3]:

@@ -867,6 +867,33 @@ int unet_inst_marks(const uint8_t* mask, const int32_t* labels, long long n, con
 int unet_inst_ids(const uint8_t* mask, const int32_t* labels, const int32_t* offs, long long n, const uint32_t* split8, uint32_t* ids,
                   void* stream);
 
+/* ------------------------------------------------------- polygon burning --
+ * Rings burnt into a uint8 [H, W] class mask (csrc/rasterize.hip, unet_amd/rasterize.py, DESIGN 3.21, where the rules are): the pixel
+ * centre decides, the fill is even-odd over the rings of a feature, the feature with the highest index wins.  xy holds V vertices (x, y) as
+ * int32 fixed point with 8 fractional bits, |x|, |y| <= 2^29; ring_start (R + 1 words) is the CSR of the rings over the vertices;
+ * vring[i] = the ring of vertex i; ring_feature[r] = the feature of ring r; values[f] = the burn value of feature f, F < 2^23 features.
+ * 1 <= H, W < 2^20; V, R and the number of crossings M are in 1..2^31 - 1.  Edge i runs from vertex i to the next vertex of its ring (the
+ * first one behind the last); rings of fewer than 3 vertices have no edges.
+ * ras_count: counts[i] = the rows y of 0 .. H - 1 with min(Y0, Y1) <= 256 y + 128 < max(Y0, Y1) of edge i.  info (2 words) is reset;
+ *   info[1] gains bit 0 if a coordinate is outside +-2^29 and bit 1 if ring_start / vring do not hold a vertex (such vertices count 0).
+ * ras_scan: offs = the exclusive scan of counts in int64, info[0] = the total; blocks holds unet_ras_scan_words(n) words.
+ * ras_emit: keys[offs[i] + t] = ring_feature << 40 | y << 20 | k for the t-th row y of edge i, k = ceil((X* - 128) / 256) clamped to 0 .. W,
+ *   X* = X0 + (256 y + 128 - Y0)(X1 - X0) / (Y1 - Y0) exactly (int64 floor division); positions outside 0 .. M - 1 are not written.
+ * ras_spans: the plane ([H, W] uint32) and *bad are zeroed; then for the sorted keys every pair 2j, 2j + 1 of one (feature, row) takes the
+ *   maximum of (feature + 1) << 8 | values[feature] into plane[row, k0 .. k1 - 1], one wavefront per pair.  Pairs whose keys differ above
+ *   bit 20, or name a feature, row or column outside F, H, W, are counted in *bad and burn nothing.  M = 0: the two resets only.
+ * ras_resolve: out[p] = plane[p] ? plane[p] & 255 : (keep ? out[p] : fill), in 16-byte accesses where plane and out are 16-byte aligned.
+ * The one atomic is a maximum of integers.  Bad arguments return -1 before any launch. */
+int unet_ras_count(const int32_t* xy, const long long* ring_start, const int32_t* vring, long long V, long long R, int H, int32_t* counts,
+                   long long* info, void* stream);
+long long unet_ras_scan_words(long long n);
+int unet_ras_scan(const int32_t* counts, long long n, long long* offs, long long* blocks, long long* info, void* stream);
+int unet_ras_emit(const int32_t* xy, const long long* ring_start, const int32_t* vring, const int32_t* ring_feature, long long V, long long R,
+                  int H, int W, const long long* offs, long long M, long long* keys, void* stream);
+int unet_ras_spans(const long long* keys, long long M, const uint8_t* values, long long F, int H, int W, uint32_t* plane, long long* bad,
+                   void* stream);
+int unet_ras_resolve(const uint32_t* plane, int H, int W, int fill, int keep, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,9 @@ VECTOR_SIMPLIFY = None
 # instance.  INSTANCES_RASTER False | True: <merged raster stem>_instances.tif, a uint32 raster of the instance ids (0 off the split classes)
 INSTANCES = None
 INSTANCES_RASTER = False
+# a mask_path that ends in .geojson / .json holds polygons instead of a raster: Create_tiles burns them on the GPU onto the image's grid
+# (unet_amd/rasterize.py) with this integer property as the class id
+MASK_ATTRIBUTE = "class"
 
 
 def main():
@@ -123,7 +126,7 @@ def main():
     if Create_tiles:
         from create_tiles_unet import split_raster
         split_raster(path_to_raster=image_path, path_to_mask=mask_path, base_dir=base_dir, patch_size=patch_size,
-                     patch_overlap=patch_overlap, split=split, max_empty=max_empty, class_zero=class_zero)
+                     patch_overlap=patch_overlap, split=split, max_empty=max_empty, class_zero=class_zero, mask_attribute=MASK_ATTRIBUTE)
     if Train:
         from train import train_func
         train_func(data_path, existing_model, model_path, description, BATCH_SIZE, visualize_data_example, enable_regression,

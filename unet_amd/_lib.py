@@ -287,6 +287,12 @@ _sig = {
     "unet_inst_canonical": (i, [vp, ll, vp, vp, vp, vp]),
     "unet_inst_marks": (i, [vp, vp, ll, C.POINTER(C.c_uint32), vp, vp]),
     "unet_inst_ids": (i, [vp, vp, vp, ll, C.POINTER(C.c_uint32), vp, vp]),
+    "unet_ras_count": (i, [vp, vp, vp, ll, ll, i, vp, vp, vp]),
+    "unet_ras_scan_words": (ll, [ll]),
+    "unet_ras_scan": (i, [vp, ll, vp, vp, vp, vp]),
+    "unet_ras_emit": (i, [vp, vp, vp, vp, ll, ll, i, i, vp, ll, vp, vp]),
+    "unet_ras_spans": (i, [vp, ll, vp, ll, i, i, vp, vp, vp]),
+    "unet_ras_resolve": (i, [vp, i, i, i, i, vp, vp]),
 }
 # bf16-storage twins: same argument lists (every tensor is a void pointer on this side)
 for _n in ("bn_stats", "affine_act", "bn_bwd_reduce", "bn_bwd_apply", "maxpool3x3s2", "maxpool3x3s2_bwd", "avgpool2_ceil",

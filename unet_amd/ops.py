@@ -1864,6 +1864,102 @@ def inst_ids(mask: torch.Tensor, labels: torch.Tensor, offs: torch.Tensor, class
     check(lib.unet_inst_ids(mask.data_ptr(), labels.data_ptr(), offs.data_ptr(), mask.numel(), words, ids.data_ptr(), _stream()), "inst_ids")
 
 
+# ---------------------------------------------------------------------------------------------- polygon burning (csrc/rasterize.hip)
+
+RAS_MAX_SIDE = 2 ** 20           # H, W < 2^20: row and column fit the 20-bit fields of a crossing's key
+RAS_MAX_COORD = 2 ** 29          # |x|, |y| <= 2^21 pixels in 1/256 pixel
+RAS_MAX_FEATURES = 2 ** 23       # (feature + 1) << 8 fits the uint32 word of the priority plane
+RAS_MAX_CROSSINGS = 2 ** 31
+
+
+def check_raster_shape(what: str, shape) -> tuple:
+    """(H, W) with 1 <= H, W < 2^20: refused from the shape alone"""
+    if not isinstance(shape, (tuple, list, torch.Size)) or len(shape) != 2 or any(isinstance(s, bool) or not hasattr(s, "__index__") for s in shape):
+        raise ValueError(f"{what}: expected a shape (H, W) of two ints, got {shape!r}")
+    H, W = int(shape[0]), int(shape[1])
+    if not (1 <= H < RAS_MAX_SIDE and 1 <= W < RAS_MAX_SIDE):
+        raise ValueError(f"{what}: H and W must lie in 1..2^20 - 1, got {H} x {W}")
+    return H, W
+
+
+def _ras_tensor(what: str, name: str, t: torch.Tensor, dtype, shape=None, numel=None):
+    _pp_tensor(what, name, t, dtype, numel=numel)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+
+
+def _ras_rings(what: str, xy: torch.Tensor, ring_start: torch.Tensor, vring: torch.Tensor, V: int, R: int):
+    _vec_count(what, "V", V)
+    _vec_count(what, "R", R)
+    _ras_tensor(what, "xy", xy, torch.int32, shape=(V, 2))
+    _ras_tensor(what, "ring_start", ring_start, torch.int64, shape=(R + 1,))
+    _ras_tensor(what, "vring", vring, torch.int32, shape=(V,))
+
+
+def ras_count(xy: torch.Tensor, ring_start: torch.Tensor, vring: torch.Tensor, V: int, R: int, H: int, counts: torch.Tensor, info: torch.Tensor):
+    """counts[i] = the row centres of 0 .. H - 1 that the edge from vertex i to the next vertex of its ring crosses; info (int64[2]) is reset
+    and info[1] becomes non-zero if a coordinate lies outside +-2^29 (bit 0) or the ring arrays do not hold a vertex (bit 1)"""
+    _ras_rings("ras_count", xy, ring_start, vring, V, R)
+    check_raster_shape("ras_count", (H, 1))
+    _ras_tensor("ras_count", "counts", counts, torch.int32, numel=V)
+    _ras_tensor("ras_count", "info", info, torch.int64, numel=2)
+    check(lib.unet_ras_count(xy.data_ptr(), ring_start.data_ptr(), vring.data_ptr(), V, R, H, counts.data_ptr(), info.data_ptr(), _stream()), "ras_count")
+
+
+def ras_scan_words(n: int) -> int:
+    """int64 words of the block-sum workspace of ras_scan over n counts"""
+    return int(lib.unet_ras_scan_words(int(n)))
+
+
+def ras_scan(counts: torch.Tensor, n: int, offs: torch.Tensor, blocks: torch.Tensor, info: torch.Tensor):
+    """offs (int64, n) = the exclusive scan of counts (int32, n); info[0] = the total"""
+    _vec_count("ras_scan", "n", n)
+    _ras_tensor("ras_scan", "counts", counts, torch.int32, numel=n)
+    _ras_tensor("ras_scan", "offs", offs, torch.int64, numel=n)
+    _ras_tensor("ras_scan", "blocks", blocks, torch.int64, numel=ras_scan_words(n))
+    _ras_tensor("ras_scan", "info", info, torch.int64, numel=2)
+    check(lib.unet_ras_scan(counts.data_ptr(), n, offs.data_ptr(), blocks.data_ptr(), info.data_ptr(), _stream()), "ras_scan")
+
+
+def ras_emit(xy: torch.Tensor, ring_start: torch.Tensor, vring: torch.Tensor, ring_feature: torch.Tensor, V: int, R: int, H: int, W: int,
+             offs: torch.Tensor, M: int, keys: torch.Tensor):
+    """keys[offs[i] + t] = feature << 40 | row << 20 | k of the t-th crossing of edge i (unet_hip.h)"""
+    _ras_rings("ras_emit", xy, ring_start, vring, V, R)
+    check_raster_shape("ras_emit", (H, W))
+    _vec_count("ras_emit", "M", M)
+    _ras_tensor("ras_emit", "ring_feature", ring_feature, torch.int32, shape=(R,))
+    _ras_tensor("ras_emit", "offs", offs, torch.int64, numel=V)
+    _ras_tensor("ras_emit", "keys", keys, torch.int64, shape=(M,))
+    check(lib.unet_ras_emit(xy.data_ptr(), ring_start.data_ptr(), vring.data_ptr(), ring_feature.data_ptr(), V, R, H, W, offs.data_ptr(), M,
+                            keys.data_ptr(), _stream()), "ras_emit")
+
+
+def ras_spans(keys: Optional[torch.Tensor], M: int, values: Optional[torch.Tensor], F: int, plane: torch.Tensor, bad: torch.Tensor):
+    """zeroes plane (int32 [H, W], read as uint32) and bad (int64[1]); then every pair of the M sorted keys burns (feature + 1) << 8 | value
+    into its span by an atomic maximum, and bad counts the pairs that are not one (feature, row).  M = 0 (keys, values None): the resets only"""
+    H, W = check_raster_shape("ras_spans", plane.shape if isinstance(plane, torch.Tensor) else ())
+    if isinstance(M, bool) or not isinstance(M, int) or not 0 <= M < RAS_MAX_CROSSINGS or M % 2:
+        raise ValueError(f"ras_spans: M must be an even int in 0..2^31 - 1, got {M!r}")
+    if isinstance(F, bool) or not isinstance(F, int) or not 0 <= F < RAS_MAX_FEATURES or (M and not F):
+        raise ValueError(f"ras_spans: F must be an int under 2^23, and at least 1 with crossings, got {F!r}")
+    if M:
+        _ras_tensor("ras_spans", "keys", keys, torch.int64, shape=(M,))
+        _ras_tensor("ras_spans", "values", values, torch.uint8, shape=(F,))
+    _ras_tensor("ras_spans", "plane", plane, torch.int32, shape=(H, W))
+    _ras_tensor("ras_spans", "bad", bad, torch.int64, numel=1)
+    check(lib.unet_ras_spans(_p(keys if M else None), M, _p(values if M else None), F, H, W, plane.data_ptr(), bad.data_ptr(), _stream()), "ras_spans")
+
+
+def ras_resolve(plane: torch.Tensor, fill: int, keep: bool, out: torch.Tensor):
+    """out [H, W] uint8 = plane & 255 where the plane is non-zero; elsewhere what out held (keep) or fill"""
+    H, W = check_raster_shape("ras_resolve", plane.shape if isinstance(plane, torch.Tensor) else ())
+    _ras_tensor("ras_resolve", "plane", plane, torch.int32, shape=(H, W))
+    _ras_tensor("ras_resolve", "out", out, torch.uint8, shape=(H, W))
+    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 255:
+        raise ValueError(f"ras_resolve: fill must be an int in 0..255, got {fill!r}")
+    check(lib.unet_ras_resolve(plane.data_ptr(), H, W, fill, int(bool(keep)), out.data_ptr(), _stream()), "ras_resolve")
+
+
 # ---------------------------------------------------------------------------------------------- GeoTIFF strips on the device (csrc/tiff_encode.hip)
 
 def tiff_lzw_cap(n: int) -> int:
