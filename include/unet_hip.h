@@ -73,7 +73,10 @@ typedef struct {
                                <= 64 input / output channels or < 3 GFLOP stay on the 64x64-blocked general kernel); 2: the GEMM kernel for all; 0: never */
     int wgrad_narrow;       /* 1: the narrow-output (80 < Cout <= 112) flattened-tap fp32 weight-gradient kernel (default); 2: the same without the
                                4-row v_mfma_f32_4x4x1 sliver for 97..100 output channels (seven 16-row tiles: A/B, cross-check); 3: as 1, and the
-                               general fp32 kernel without the pixel sub-splits of layers with <= 32 input / output channels (A/B) */
+                               general fp32 kernel without the pixel sub-splits of layers with <= 32 input / output channels (A/B); 4: as 1,
+                               and every launch of the narrow-output kernel stages its tiles through registers (A/B, cross-check: same bits).
+                               With 1, 2 and 3 a launch whose column blocks each read at most two of the three tap rows loads its tiles by
+                               LDS-DMA (buffer loads straight to LDS); unet_conv2d_wgrad_dma tells which form a descriptor gets */
     int plan_batch;         /* 0 (default): the conv planner sizes tiles / split reductions for the batch of the descriptor.  n > 0: it plans as
                                if the batch were n images, whatever N is -- with 1, every image of a batch runs exactly the kernels, tiles and split
                                chains it would run alone: predictions become bit-identical ACROSS batch sizes (the reference predicts tile by
@@ -208,6 +211,8 @@ typedef struct {
     const unet_tuning* tuning;           /* NULL = defaults */
 } unet_wgrad_desc;
 size_t unet_conv2d_wgrad_workspace(const unet_wgrad_desc* d);
+/* 1: the launch loads its tiles by LDS-DMA (see unet_tuning.wgrad_narrow), 0: through registers or on another kernel, -1: bad descriptor */
+int unet_conv2d_wgrad_dma(const unet_wgrad_desc* d);
 int unet_conv2d_wgrad(const unet_wgrad_desc* d, void* stream);
 
 /* ----------------------------------------------------------- batch norm --

@@ -167,6 +167,7 @@ _sig = {
     "unet_row_softmax": (i, [vp, i, i, vp, i, i, ll, i, vp]),
     "unet_row_softmax_bwd": (i, [vp, i, i, vp, i, i, vp, i, i, ll, i, vp]),
     "unet_conv2d_wgrad_workspace": (sz, [C.POINTER(WgradDesc)]),
+    "unet_conv2d_wgrad_dma": (i, [C.POINTER(WgradDesc)]),
     "unet_conv2d_wgrad": (i, [C.POINTER(WgradDesc), vp]),
     "unet_bn_stats_rows": (i, [ll]),
     "unet_bn_stats": (i, [vp, i, i, ll, i, vp, vp]),

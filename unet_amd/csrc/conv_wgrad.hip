@@ -21,6 +21,7 @@
 #include <utility>
 
 #include "common.h"
+#include "wgrad_plan.h"
 
 namespace {
 
@@ -394,14 +395,20 @@ __global__ __launch_bounds__(256, 2) void wgrad16_kernel(const WArgs a) {
 // column group cg), so the B operand IS the register the 16x16x4 tiles of that column tile use (lane 16 kk + 4 cg + j = pixel kk, column
 // 4 cg + j), and A is dy[pixel 4*step + kk][16 KT + (lane & 3)].  D: lane l, VGPR r = row 16 KT + r, column l & 15, summed over the pixels
 // of class kk = l >> 4; the four classes meet in the epilogue, (kk0 + kk1) + (kk2 + kk3), two lane exchanges.
-template <int KT, int NTW, bool SLV = false>
+// DMA: the tiles come by buffer loads straight to LDS, the next tile's behind the MFMAs of the current one, one barrier per tile and no staging
+// registers (74 752 bytes of LDS: still two workgroups per CU); the planner picks it per launch (flat_dma_fits), the pipeline is described
+// at its loop below.  The first workgroup column then reads its dy items back from the LDS tile and keeps the bias sums in registers: the same
+// additions in the same order as the register-staged form.
+template <int KT, int NTW, bool SLV = false, bool DMA = false>
 __global__ __launch_bounds__(256, 2) void wgrad_flat_kernel(const WArgs a) {
     constexpr int PT = 32, HW = 34, HPIX = 3 * HW, LD = 112, Q = LD / 4;
     constexpr int DIT = (PT * Q + 255) / 256, XIT = (HPIX * Q + 255) / 256;
+    // DMA form: two dy tiles, and every ring slot rounded up to whole 1 KiB wave pieces (15: the last 8 items of a row's last piece land in the pad)
+    constexpr int SLOT = DMA ? 15 * 256 : HW * LD;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* dyT = smem;              // [PT][LD]
-    float* xh = smem + PT * LD;     // [HPIX][LD]
+    float* dyT = smem;                              // [DMA ? 2 : 1][PT][LD]
+    float* xh = smem + (DMA ? 2 : 1) * PT * LD;     // [3][SLOT]: rows of [HW][LD]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, kk = lane >> 4;
@@ -428,7 +435,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_flat_kernel(const WArgs a) {
 #pragma unroll
     for (int q = 0; q < NTW; ++q) {
         const int n = ((nb * 4 + wave) * NTW + q) * 16 + l15;
-        const int nn = n < NTOT ? n : 0;          // columns beyond 9*CW compute garbage that is never stored
+        // columns beyond 9*CW compute garbage that is never stored.  DMA form: they read the LAST real column (tap row 2 is one this block
+        // reads anyway; the slot of tap row 0 may be the landing slot)
+        const int nn = n < NTOT ? n : (DMA ? NTOT - 1 : 0);
         const int t = nn / CW, c = nn - t * CW;
         const int r = t / 3, s_ = t - 3 * r;
         bfix[q] = (s_ + kk) * LD + c;
@@ -446,10 +455,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_flat_kernel(const WArgs a) {
 #pragma unroll
     for (int q = 0; q < (SLV ? NTW : 1); ++q) sacc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    // Staging (global -> registers -> LDS); pixels outside the image are zero, channels beyond the chunk are never read
-    // back.  tile = (img * tiles_x + tx) * OH + oy.  The 35-accumulator form has 32 registers to spare: it fetches the next
-    // tile's dy rows and its one new input row BEFORE the MFMA loop of the current tile and stores them after it.
-    constexpr bool PF = (KT * NTW + (SLV ? NTW : 0) <= 36);
+    // tile = (img * tiles_x + tx) * OH + oy
     constexpr int RIT = (HW * Q + 255) / 256;     // float4 items per thread per input row
     const int cw4 = (CW + 3) & ~3;
     struct TilePos { int oy, ox0; const float* dyb; const float* xb; };
@@ -464,6 +470,44 @@ __global__ __launch_bounds__(256, 2) void wgrad_flat_kernel(const WArgs a) {
         t.xb = a.x + (size_t)img * a.IH * a.IW * a.x_cs + a.x_co + c0;
         return t;
     };
+
+    // the MFMA steps of one tile: tap row r reads input row oy - 1 + r; ab / sb: the lane's bases in the dy tile
+    auto mma_tile = [&](int oy, int ab, int sb) {
+        int bq[NTW];
+#pragma unroll
+        for (int q = 0; q < NTW; ++q) bq[q] = bfix[q] + ((oy + 2 + brow[q]) % 3) * SLOT;
+        // (a full unroll hoists all 96 operand loads and spills; the 42-accumulator form only has room for one step's operands)
+        auto mma_step = [&](int step) {
+            float av[KT], bv[NTW];
+            float as_ = 0.f;
+#pragma unroll
+            for (int m = 0; m < KT; ++m) av[m] = dyT[ab + step * 4 * LD + m * 16];
+            if constexpr (SLV) as_ = dyT[sb + step * 4 * LD];
+#pragma unroll
+            for (int q = 0; q < NTW; ++q) bv[q] = xh[bq[q] + step * 4 * LD];
+#pragma unroll
+            for (int m = 0; m < KT; ++m)
+#pragma unroll
+                for (int q = 0; q < NTW; ++q) acc[m][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], bv[q], acc[m][q], 0, 0, 0);
+            if constexpr (SLV) {
+#pragma unroll
+                for (int q = 0; q < NTW; ++q) sacc[q] = __builtin_amdgcn_mfma_f32_4x4x1f32(as_, bv[q], sacc[q], 0, 0, 0);
+            }
+        };
+        if constexpr (KT * NTW + (SLV ? NTW : 0) > 36) {
+#pragma unroll 1
+            for (int step = 0; step < PT / 4; ++step) mma_step(step);
+        } else {
+#pragma unroll 2
+            for (int step = 0; step < PT / 4; ++step) mma_step(step);
+        }
+    };
+
+    if constexpr (!DMA) {
+    // ---- register-staged form (global -> registers -> LDS); pixels outside the image are zero, channels beyond the chunk are never read
+    // back.  The 35-accumulator form has 32 registers to spare: it fetches the next tile's dy rows and its one new input row BEFORE the
+    // MFMA loop of the current tile and stores them after it.
+    constexpr bool PF = (KT * NTW + (SLV ? NTW : 0) <= 36);
     auto load_dy = [&](const TilePos& t, float4 (&r)[DIT]) {
 #pragma unroll
         for (int it = 0; it < DIT; ++it) {
@@ -492,7 +536,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_flat_kernel(const WArgs a) {
         }
     };
     auto store_row = [&](const TilePos& t, int hy, const float4 (&r)[RIT]) {
-        float* dst = xh + ((t.oy + 2 + hy) % 3) * (HW * LD);               // ring slot of row iy = (iy + 3) % 3
+        float* dst = xh + ((t.oy + 2 + hy) % 3) * SLOT;                    // ring slot of row iy = (iy + 3) % 3
 #pragma unroll
         for (int j = 0; j < RIT; ++j) {
             const int e = tid + j * 256;
@@ -599,34 +643,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_flat_kernel(const WArgs a) {
             prefetch_rolling(nx, pd, px);
             if (do_bias) bias_add(pd);
         }
-        int bq[NTW];
-#pragma unroll
-        for (int q = 0; q < NTW; ++q) bq[q] = bfix[q] + ((oy + 2 + brow[q]) % 3) * (HW * LD);   // tap row r reads input row oy - 1 + r
-        // (a full unroll hoists all 96 operand loads and spills; the 42-accumulator form only has room for one step's operands)
-        auto mma_step = [&](int step) {
-            float av[KT], bv[NTW];
-            float as_ = 0.f;
-#pragma unroll
-            for (int m = 0; m < KT; ++m) av[m] = dyT[abase + step * 4 * LD + m * 16];
-            if constexpr (SLV) as_ = dyT[sbase + step * 4 * LD];
-#pragma unroll
-            for (int q = 0; q < NTW; ++q) bv[q] = xh[bq[q] + step * 4 * LD];
-#pragma unroll
-            for (int m = 0; m < KT; ++m)
-#pragma unroll
-                for (int q = 0; q < NTW; ++q) acc[m][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], bv[q], acc[m][q], 0, 0, 0);
-            if constexpr (SLV) {
-#pragma unroll
-                for (int q = 0; q < NTW; ++q) sacc[q] = __builtin_amdgcn_mfma_f32_4x4x1f32(as_, bv[q], sacc[q], 0, 0, 0);
-            }
-        };
-        if constexpr (!PF) {
-#pragma unroll 1
-            for (int step = 0; step < PT / 4; ++step) mma_step(step);
-        } else {
-#pragma unroll 2
-            for (int step = 0; step < PT / 4; ++step) mma_step(step);
-        }
+        mma_tile(oy, abase, sbase);
         if (has_next) {
             __syncthreads();                 // everyone is done reading this tile (the new row replaces row oy - 1)
             if (PF && rolling) { store_dy(pd); store_row(nx, 2, px); }
@@ -637,7 +654,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_flat_kernel(const WArgs a) {
             __syncthreads();
         }
     }
-
     if (do_bias) {          // channel c adds the item sums of its quad in item order
         __syncthreads();
         const float* red = smem + (PT + HPIX) * LD;
@@ -646,6 +662,119 @@ __global__ __launch_bounds__(256, 2) void wgrad_flat_kernel(const WArgs a) {
             for (int e = tid >> 2; e < PT * Q; e += Q) t += red[e * 4 + (tid & 3)];
             a.bpart[(size_t)split * a.Cout + tid] = t;
         }
+    }
+    } else {
+    // ---- LDS-DMA form: no staging registers, no store phase, one barrier per tile.  The planner only sends launches here in which every
+    // column block reads at most TWO of the three tap rows (rmin .. rmax below): while tile oy is multiplied, the dy row of tile oy + 1 lands in
+    // the other dy tile and its one new input row, oy + rmax, in the ring slot of the row this block does not read -- (oy + rmax) - (oy - 1 + r)
+    // is 1 or 2 for both tap rows r the block reads, never a multiple of 3.  Every item is one buffer load to LDS: a wave instruction writes the
+    // 64 items e = 256 it + 64 wave + lane at 16 e bytes, where store_dy / store_row put them.  The descriptor covers ONE pixel row of the
+    // slice (no record at all for a row outside the image); a pixel outside the row and a channel quad that is never read back carry an
+    // offset beyond every record: the range check answers them with zeros and sends no request.
+    typedef __attribute__((address_space(3))) void* lds_ptr;
+    constexpr unsigned OOB = 0x80000000u;
+    int n_lo = nb * 64 * NTW, n_hi = (n_lo + 64 * NTW < NTOT ? n_lo + 64 * NTW : NTOT) - 1;
+    if (n_lo >= NTOT) n_lo = n_hi = NTOT - 1;                 // a block of spare columns only: they all read the last real one
+    const int rmin = n_lo / (3 * CW), rmax = n_hi / (3 * CW);          // tap row of column n = (n / CW) / 3
+    const int dy_row_b = (a.OW * a.dy_cs - a.dy_co) * 4, x_row_b = (a.IW * a.x_cs - a.x_co - c0) * 4;    // bytes from a row's first item to the row's end
+    unsigned dvo[DIT], xvo[RIT];            // byte offsets of the thread's items inside the pixel row, set up once per column strip
+    auto strip_setup_dma = [&](int ox0) {
+#pragma unroll
+        for (int it = 0; it < DIT; ++it) {
+            const int e = tid + it * 256;
+            const int p = e / Q, q = e - p * Q;
+            const bool ok = (e < PT * Q) && (ox0 + p) < a.OW && 4 * q < a.Cout4;
+            dvo[it] = ok ? (unsigned)((ox0 + p) * a.dy_cs + 4 * q) * 4u : OOB;
+        }
+#pragma unroll
+        for (int j = 0; j < RIT; ++j) {
+            const int e = tid + j * 256;
+            const int hx = e / Q, q = e - hx * Q;
+            const int ix = ox0 - 1 + hx;
+            const bool ok = (e < HW * Q) && ix >= 0 && ix < a.IW && 4 * q < cw4;
+            xvo[j] = ok ? (unsigned)(ix * a.x_cs + 4 * q) * 4u : OOB;
+        }
+    };
+    auto dma_dy = [&](const TilePos& t, int buf) {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(t.dyb), 0, dy_row_b, 0x00020000);
+        float* dst = dyT + buf * (PT * LD) + wave * 256;
+#pragma unroll
+        for (int it = 0; it < DIT; ++it)
+            if (it * 256 + wave * 64 < PT * Q)          // (whole waves: PT * Q = 14 * 64)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(dst + it * 1024), 16, (int)dvo[it], 0, 0, 0);
+    };
+    auto dma_row = [&](const TilePos& t, int hy) {                      // input row oy - 1 + hy into its ring slot
+        const int iy = t.oy - 1 + hy;
+        const bool rowok = iy >= 0 && iy < a.IH;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(t.xb) + (size_t)(rowok ? iy : 0) * a.IW * a.x_cs, 0,
+                                                                            rowok ? x_row_b : 0, 0x00020000);
+        float* dst = xh + ((t.oy + 2 + hy) % 3) * SLOT + wave * 256;
+#pragma unroll
+        for (int j = 0; j < RIT; ++j)
+            if (j * 256 + wave * 64 < HW * Q)           // (the last piece is partly pad: SLOT)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(dst + j * 1024), 16, (int)xvo[j], 0, 0, 0);
+    };
+    // every wave waits for its own DMAs, then one barrier: behind it the tile is in LDS for all, and everyone has read the previous one.
+    // (not __syncthreads(): its fence would wait for the DMAs wherever it stands)
+    auto land_and_meet = [&]() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+    auto refill = [&](const TilePos& t, int buf) {      // a tile that starts a column strip: its dy row and all the input rows this block reads
+        strip_setup_dma(t.ox0);
+        dma_dy(t, buf);
+        for (int hy = rmin; hy <= rmax; ++hy) dma_row(t, hy);
+    };
+    // bias gradient, first workgroup column: dy no longer passes through registers, so every thread reads ITS items of the landed dy tile
+    // back from LDS (item it of thread tid, as in the register-staged form) and adds them to sums it keeps in registers -- the staging
+    // registers are gone, and the 16 KB of LDS sums would not fit.  The same additions in the same order: the same bits.
+    const bool dma_bias = a.bpart != nullptr && bx == 0;
+    float4 bsum[DIT];
+#pragma unroll
+    for (int it = 0; it < DIT; ++it) bsum[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto bias_add_tile = [&](int buf) {
+        const float4* src = reinterpret_cast<const float4*>(dyT + buf * (PT * LD)) + tid;
+#pragma unroll
+        for (int it = 0; it < DIT; ++it) {
+            if (it * 256 + 255 < PT * Q || tid < PT * Q - it * 256) {       // (only the last item is cut: PT * Q = 3 * 256 + 128)
+                const float4 v = src[it * 256];
+                bsum[it].x += v.x; bsum[it].y += v.y; bsum[it].z += v.z; bsum[it].w += v.w;
+            }
+        }
+    };
+    int cur = 0;
+    refill(tile_pos(tile_begin), 0);
+    land_and_meet();
+    for (int tile = tile_begin; tile < tile_end; ++tile) {
+        const int oy = tile % a.OH;
+        const bool has_next = tile + 1 < tile_end;
+        const bool rolling = has_next && oy + 1 < a.OH;      // the next tile is one row further down the same column strip
+        TilePos nx;
+        if (has_next) nx = tile_pos(tile + 1);
+        // (the reads come BEFORE the DMAs are issued: behind them the compiler waits for vmcnt(0) in front of any LDS read it cannot tell
+        // apart from the landing tile, which would drain the prefetch before the first MFMA; the operand reads of mma_tile do not draw that wait)
+        if (dma_bias) bias_add_tile(cur);
+        if (rolling) { dma_dy(nx, cur ^ 1); dma_row(nx, rmax); }
+        mma_tile(oy, abase + cur * (PT * LD), sbase + cur * (PT * LD));
+        if (has_next) {
+            if (!rolling) {
+                land_and_meet();             // everyone is done reading this tile: the new strip's rows may land in any slot
+                refill(nx, cur ^ 1);
+            }
+            land_and_meet();
+            cur ^= 1;
+        }
+    }
+    if (dma_bias) {         // the dy tiles are dead: the item sums meet there, channel c adds those of its quad in item order
+        land_and_meet();
+        float4* red4 = reinterpret_cast<float4*>(smem) + tid;
+#pragma unroll
+        for (int it = 0; it < DIT; ++it)
+            if (it * 256 + 255 < PT * Q || tid < PT * Q - it * 256) red4[it * 256] = bsum[it];
+        land_and_meet();
+        if (tid < a.Cout) {
+            float t = 0.f;
+            for (int e = tid >> 2; e < PT * Q; e += Q) t += smem[e * 4 + (tid & 3)];
+            a.bpart[(size_t)split * a.Cout + tid] = t;
+        }
+    }
     }
     // ---- write partials: part[split][tap][k][c] ----
     const size_t KC_ = (size_t)a.Cout * a.Cin;
@@ -1354,22 +1483,25 @@ __global__ __launch_bounds__(256) void wgrad_bias_reduce_kernel(const float* __r
     if (q == 0 && c < Cout) dbias[c] = (float)(((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl]);
 }
 
-// unet_tuning.wgrad_narrow: the narrow-output kernel (wgrad_flat_kernel) for 80 < Cout <= 112 (0 falls back to the 64x64-tiled kernel);
+// unet_tuning.wgrad_narrow: the narrow-output kernel (wgrad_flat_kernel) for 80 < Cout <= 112 (0 falls back to the 64x64-tiled kernel;
+// 4 keeps its register-staged form where the planner would pick the LDS-DMA form);
 // .wgrad_1x1: the 128x128-tiled GEMM kernel for 1x1 weight gradients
 struct WPlan {
     unet_tuning tune;
     WArgs k;
     int ptw, splits, T, narrow, gemm1x1, small1x1, ps, bf16;
+    int dma;         // narrow: the LDS-DMA form of wgrad_flat_kernel
     int nsub;        // partial images per workgroup (wgrad_kernel's pixel sub-splits of narrow layers): the reduce kernels sum splits * nsub slices
     long long pix_per_block;
     size_t lds_bytes, lds_bytes16;
 };
 
-int make_wplan(const unet_wgrad_desc* d, WPlan* p) {
+// (a plan query that launches nothing passes need_dw = false: it has no output to name)
+int make_wplan(const unet_wgrad_desc* d, WPlan* p, bool need_dw = true) {
     UNET_CHECK_ARG(d != nullptr, "wgrad: null desc");
     p->tune = unetconv::tuning_of(d->tuning);
     UNET_CHECK_ARG(p->tune.wgrad_mfma_shape == 16 || p->tune.wgrad_mfma_shape == 32, "wgrad: unet_tuning.wgrad_mfma_shape must be 16 or 32 (start from unet_tuning_default())");
-    UNET_CHECK_ARG(d->x && d->dy && d->dw, "wgrad: null tensor pointer");
+    UNET_CHECK_ARG(d->x && d->dy && (d->dw || !need_dw), "wgrad: null tensor pointer");
     UNET_CHECK_ARG(d->ks == 1 || d->ks == 3, "wgrad: ks must be 1 or 3");
     UNET_CHECK_ARG(d->stride == 1 || d->stride == 2, "wgrad: stride must be 1 or 2");
     UNET_CHECK_ARG(!(d->ks == 1 && d->stride != 1), "wgrad: 1x1 stride 2 unsupported");
@@ -1392,6 +1524,7 @@ int make_wplan(const unet_wgrad_desc* d, WPlan* p) {
     k.OH = d->OH; k.OW = d->OW; k.Cout = d->Cout; k.Cout4 = unet::roundup(d->Cout, vec);
     p->T = d->ks * d->ks;
     p->nsub = 1;
+    p->dma = 0;
     p->ptw = d->OW >= 32 ? 32 : (d->OW >= 16 ? 16 : 8);
     const int pt = p->bf16 ? (d->stride == 1 ? 128 : 32) : (d->stride == 1 ? 64 : 32);   // bf16: four (stride 2: one) MFMA k-blocks of 32 pixels
     const int pth = pt / p->ptw;
@@ -1413,6 +1546,9 @@ int make_wplan(const unet_wgrad_desc* d, WPlan* p) {
         const int ntw = d->Cout > 96 ? 5 : 7;                     // column tiles per wave (KT = 7 / 6 output-channel tiles)
         k.nnb = unet::cdiv(unet::cdiv(9 * k.cw, 16), 4 * ntw);
         cols = nch * k.nnb;
+        // (one pixel row of either operand is a buffer descriptor's range: byte offsets below 2^31)
+        p->dma = p->tune.wgrad_narrow != 4 && flat_dma_fits(d->Cin, k.cw, k.nnb, ntw) && (long long)d->IW * d->x_cs * 4 < (1ll << 31) &&
+                 (long long)d->OW * d->dy_cs * 4 < (1ll << 31);
     }
     // heads: 1x1 with <= 16 output channels and <= 1024 input channels -> FMA kernel, one partial row per (workgroup, pixel lane)
     p->small1x1 = (!p->bf16 && d->ks == 1 && d->Cout <= 16 && k.Cin4 <= 512 && p->tune.wgrad_1x1) ? 1 : 0;
@@ -1581,6 +1717,12 @@ extern "C" size_t unet_conv2d_wgrad_workspace(const unet_wgrad_desc* d) {
     return (size_t)p.splits * p.nsub * p.T * d->Cout * d->Cin + (size_t)p.splits * d->Cout;
 }
 
+extern "C" int unet_conv2d_wgrad_dma(const unet_wgrad_desc* d) {
+    WPlan p;
+    if (make_wplan(d, &p, false) != UNET_OK) return -1;
+    return p.dma;
+}
+
 extern "C" int unet_conv2d_wgrad(const unet_wgrad_desc* d, void* stream) {
     WPlan p;
     int rc = make_wplan(d, &p);
@@ -1621,16 +1763,26 @@ extern "C" int unet_conv2d_wgrad(const unet_wgrad_desc* d, void* stream) {
         UNET_CHECK_LAUNCH();
         rc = UNET_OK;
     } else if (p.narrow) {
-        const size_t lds = (size_t)(32 + 3 * 34) * 112 * sizeof(float) + (size_t)4 * 256 * 16;      // the two tiles + the bias item sums [DIT = 4][256] float4
+        // register-staged form: the two tiles + the bias item sums [DIT = 4][256] float4; LDS-DMA form: two dy tiles + three ring slots of 15 KiB
+        const size_t lds = p.dma ? (size_t)(2 * 32 * 112 + 3 * 15 * 256) * sizeof(float)
+                                 : (size_t)(32 + 3 * 34) * 112 * sizeof(float) + (size_t)4 * 256 * 16;
         const dim3 grid(unet::cdiv(d->Cin, p.k.cw) * p.k.nnb, unet::roundup(p.splits, 8));
         static unsigned long long configured = 0;   // one bit per device
         if (unet::first_use_on_device(&configured)) {
             UNET_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_flat_kernel<7, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             UNET_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_flat_kernel<6, 5, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             UNET_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_flat_kernel<6, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            UNET_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_flat_kernel<7, 5, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            UNET_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_flat_kernel<6, 5, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            UNET_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_flat_kernel<6, 7, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         }
         // 97..100 output channels (the 100 -> 100 pair): six 16-row tiles + a 4-row sliver; unet_tuning.wgrad_narrow = 2 keeps the seven-tile form (A/B)
-        if (d->Cout > 96 && d->Cout <= 100 && p.tune.wgrad_narrow != 2) hipLaunchKernelGGL((wgrad_flat_kernel<6, 5, true>), grid, dim3(256), lds, st, p.k);
+        const bool sliver = d->Cout > 96 && d->Cout <= 100 && p.tune.wgrad_narrow != 2;
+        if (p.dma) {
+            if (sliver) hipLaunchKernelGGL((wgrad_flat_kernel<6, 5, true, true>), grid, dim3(256), lds, st, p.k);
+            else if (d->Cout > 96) hipLaunchKernelGGL((wgrad_flat_kernel<7, 5, false, true>), grid, dim3(256), lds, st, p.k);
+            else hipLaunchKernelGGL((wgrad_flat_kernel<6, 7, false, true>), grid, dim3(256), lds, st, p.k);
+        } else if (sliver) hipLaunchKernelGGL((wgrad_flat_kernel<6, 5, true>), grid, dim3(256), lds, st, p.k);
         else if (d->Cout > 96) hipLaunchKernelGGL((wgrad_flat_kernel<7, 5>), grid, dim3(256), lds, st, p.k);
         else hipLaunchKernelGGL((wgrad_flat_kernel<6, 7>), grid, dim3(256), lds, st, p.k);
         UNET_CHECK_LAUNCH();

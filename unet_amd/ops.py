@@ -535,6 +535,14 @@ def wgrad_workspace(x: TS, dy: TS, ks, stride, with_bias=False) -> int:
     return int(lib.unet_conv2d_wgrad_workspace(C.byref(d)))
 
 
+def wgrad_uses_dma(x: TS, dy: TS, ks, stride) -> bool:
+    """whether the planner sends this weight gradient to the LDS-DMA form of the narrow-output kernel (under the current tuning)"""
+    d = _wgrad_desc(x, dy, None, None, ks, stride, None, 0)
+    r = lib.unet_conv2d_wgrad_dma(C.byref(d))
+    assert r >= 0, "wgrad_uses_dma: bad descriptor"
+    return r == 1
+
+
 def conv2d_wgrad(x: TS, dy: TS, dw: torch.Tensor, ks: int, stride: int, ws: torch.Tensor, dbias=None, accumulate=False):
     d = _wgrad_desc(x, dy, dw, dbias, ks, stride, ws, accumulate)
     check(lib.unet_conv2d_wgrad(C.byref(d), _stream()), "conv2d_wgrad")
