@@ -898,6 +898,24 @@ int unet_ras_emit(const int32_t* xy, const long long* ring_start, const int32_t*
 int unet_ras_spans(const long long* keys, long long M, const uint8_t* values, long long F, int H, int W, uint32_t* plane, long long* bad,
                    void* stream);
 int unet_ras_resolve(const uint32_t* plane, int H, int W, int fill, int keep, uint8_t* out, void* stream);
+/* ras_resolve_ids: ids[p] = plane[p] ? (plane[p] >> 8) - 1 : -1 (int32 [H, W]): the feature that owns each pixel, in 16-byte accesses where
+ * plane and ids are 16-byte aligned. */
+int unet_ras_resolve_ids(const uint32_t* plane, int H, int W, int32_t* ids, void* stream);
+
+/* ------------------------------------------------------ zonal statistics --
+ * The joint histogram of a zone plane and a class mask (csrc/zonal.hip, unet_amd/zonal.py, DESIGN 3.22, where the rules are).  zones is
+ * int32 [H, W] (-1 = no zone, else 0 .. Z - 1), mask uint8 [H, W] (values 0 .. C - 1), labels int32 [H, W] or null (labels[p] = the smallest
+ * linear index of the object of pixel p; p is an anchor iff labels[p] == p; with labels H * W <= 2^31 - 1).  1 <= H, W < 2^20, 1 <= Z < 2^23,
+ * 1 <= C <= 256, Z * C < 2^31.  counts and objects are uint64 [Z, C] and ZEROED BY THE CALLER; objects is null exactly when labels is.
+ * zonal_counts: counts[z, c] += the pixels with zone z and mask value c; objects[z, c] += the anchors among them.  A pixel whose mask value
+ *   is >= C (bit 0) or whose zone lies outside -1 .. Z - 1 (bit 1) is counted nowhere and sets that bit in *bad, which is reset first.
+ *   Z * C <= unet_zonal_lds_bins(): every workgroup counts into a private table of uint32 bins in LDS (it sees fewer than 2^31 pixels) and
+ *   adds its non-zero bins to counts; otherwise the adds go to counts directly.  Every add is an integer atomic add, so the result does
+ *   not depend on the order of arrival.  16-byte accesses where zones and labels are 16-byte and mask 4-byte aligned; no access outside the
+ *   H * W elements.  Bad arguments return -1 before any launch. */
+int unet_zonal_lds_bins(void);
+int unet_zonal_counts(const int32_t* zones, const uint8_t* mask, const int32_t* labels, int H, int W, int Z, int C, long long* counts,
+                      long long* objects, long long* bad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,12 @@ VECTOR_SIMPLIFY = None
 # instance.  INSTANCES_RASTER False | True: <merged raster stem>_instances.tif, a uint32 raster of the instance ids (0 off the split classes)
 INSTANCES = None
 INSTANCES_RASTER = False
+# zonal statistics of the merged class mask (merge = True, class output), counted on the GPU (unet_amd/zonal.py): ZONES None | the path of a
+# GeoJSON file of Polygon / MultiPolygon zones (parcels, districts, stands) in the raster's coordinates; the pixels and the share of every
+# class per zone are written as <merged raster stem>_zonal.geojson with the zones' own properties.  ZONAL_OBJECTS False | True: also the
+# number of objects (components, or the instances of INSTANCES) per zone and class; an object counts in the zone of its first pixel
+ZONES = None
+ZONAL_OBJECTS = False
 # a mask_path that ends in .geojson / .json holds polygons instead of a raster: Create_tiles burns them on the GPU onto the image's grid
 # (unet_amd/rasterize.py) with this integer property as the class id
 MASK_ATTRIBUTE = "class"
@@ -110,7 +116,7 @@ MASK_ATTRIBUTE = "class"
 def main():
     global large_file, specific_class, all_classes, transforms, VALID_SCENES, self_attention, monitor, loss_func, LR_FINDER
     global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS
-    global VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY, INSTANCES, INSTANCES_RASTER
+    global VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY, INSTANCES, INSTANCES_RASTER, ZONES, ZONAL_OBJECTS
     t0 = time.time()
     if enable_extra_parameters:          # params_and_main.py:129-145
         import warnings
@@ -123,6 +129,7 @@ def main():
         TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS = None, "mean", None, None, None, None
         VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY = False, None, None
         INSTANCES, INSTANCES_RASTER = None, False
+        ZONES, ZONAL_OBJECTS = None, False
     if Create_tiles:
         from create_tiles_unet import split_raster
         split_raster(path_to_raster=image_path, path_to_mask=mask_path, base_dir=base_dir, patch_size=patch_size,
@@ -149,6 +156,8 @@ def main():
                 extra["vector_simplify"] = VECTOR_SIMPLIFY
         if INSTANCES is not None:
             extra["instances"], extra["instances_raster"] = INSTANCES, INSTANCES_RASTER
+        if ZONES is not None:
+            extra["zones"], extra["zonal_objects"] = ZONES, ZONAL_OBJECTS
         save_predictions(predict_model, predict_path, regression, merge, all_classes, specific_class, large_file, AOI, year,
                          validation_vision, class_zero, tta=TTA, **extra)
     print(f"Operation completed in {(time.time() - t0) / 60:.2f} minutes.")

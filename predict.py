@@ -33,9 +33,10 @@ slab add and finalisation), so N ranks equal 1 rank bit for bit here too.  Refus
 The output options beyond the reference, each described at ``predict_raster``: ``postprocess=`` (majority filter / sieve of the merged class
 mask, ``unet_amd/postprocess.py``), ``compress=`` / ``predictor=`` / ``tile=`` / ``overviews=`` (LZW GeoTIFFs, tiled and with overviews),
 ``vector_path=`` / ``vector=True`` with ``vector_exclude=`` and ``vector_simplify=`` (the mask's polygons as GeoJSON, ``unet_amd/vectorize.py``) and
-``instances=`` (touching objects split into instances, ``unet_amd/instances.py``).  ``check_outputs``, the first statement of both entry points,
+``instances=`` (touching objects split into instances, ``unet_amd/instances.py``) and ``zones_path=`` / ``zones=`` with ``zonal_objects=`` (pixels, shares
+and objects of every class per polygon zone, ``unet_amd/zonal.py``).  ``check_outputs``, the first statement of both entry points,
 checks them from the arguments alone (ValueError before the model is loaded) into one ``OutputPlan``.  ``_write_outputs`` is the one output stage,
-on rank 0 and on the assembled mask, so N ranks equal 1 rank by construction: instances, the vector file, the raster.  The plan keeps the merged
+on rank 0 and on the assembled mask, so N ranks equal 1 rank by construction: instances, the vector file, the zonal table, the raster.  The plan keeps the merged
 array where the merge assembled it while a stage needs it there: with one rank the mask goes from the argmax through the filters, the split and
 the polygonizer into the LZW encoder (``unet_amd/tiffenc.py``) on the device; the int8 ``large_file`` merge, gloo ranks and per-tile outputs use
 the host encoder of ``unet_amd/tiffio.py``: the same file.
@@ -64,6 +65,7 @@ from unet_amd.tiffio import check_compress, check_tiling, read_tiff, resolve_ove
 from unet_amd.tta import parse as tta_codes
 from unet_amd.vectorize import check_vector, epsg_of_tags, vectorize_mask
 from unet_amd.instances import Instances, check_instances
+from unet_amd.zonal import check_zones, zonal_mask
 
 
 def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_zero=False, compress=None, predictor=1,
@@ -112,6 +114,8 @@ class OutputPlan:
     vector_simplify: Optional[float] = None
     instances: Optional[Instances] = None
     instances_raster: bool = False
+    zones: bool = False                               # a zonal table is written
+    zonal_objects: bool = False
 
     mask = property(lambda p: not (p.regression or p.all_classes or p.specific_class is not None))       # the output is the class mask
     want = property(lambda p: 0 if p.regression else "all" if p.all_classes else "argmax" if p.mask else int(p.specific_class))    # _Merge.finish
@@ -120,7 +124,7 @@ class OutputPlan:
     nodata = property(lambda p: -9999 if p.regression else None)
     # a compressed raster is written from the tensor the merge assembled: on the device with one rank or RCCL, where only the bytes reach the host
     encode_in_place = property(lambda p: p.compress is not None and p.raster)
-    keep = property(lambda p: p.encode_in_place or p.vector is not None or p.instances is not None)       # the merged array stays a tensor there
+    keep = property(lambda p: p.encode_in_place or p.vector is not None or p.instances is not None or p.zones)       # the merged array stays a tensor there
 
     def needs_mask(self, subject: str, done: str, one_device: bool = True):
         """the rule of every option that works on the class mask of a merged prediction"""
@@ -134,9 +138,11 @@ class OutputPlan:
 
 def check_outputs(regression=False, all_classes=False, specific_class=None, large_file=False, merge=True, class_zero=False, blend="mean",
                   postprocess=None, compress=None, predictor=1, tile=None, overviews=None, vector=None, vector_exclude=None, vector_simplify=None,
-                  instances=None, instances_raster=False, raster=True, return_array=True, raster_arg="instances_raster") -> OutputPlan:
+                  instances=None, instances_raster=False, raster=True, return_array=True, raster_arg="instances_raster", zones=None,
+                  zonal_objects=False) -> OutputPlan:
     """Every check of the two entry points' output arguments, from the arguments alone and in one order -> the OutputPlan.  vector: vector= or
-    vector_path=; instances_raster: whether the argument named raster_arg asks for the instance raster; raster: whether out_path is given"""
+    vector_path=; instances_raster: whether the argument named raster_arg asks for the instance raster; raster: whether out_path is given;
+    zones: zones= or zones_path= (the entry points check that its output path is there)"""
     mode = OutputPlan(bool(regression), bool(all_classes), specific_class, bool(large_file), bool(merge), bool(class_zero), bool(raster))
     check_blend(blend, large_file, merge)
     post = check_postprocess(postprocess)
@@ -153,18 +159,24 @@ def check_outputs(regression=False, all_classes=False, specific_class=None, larg
     inst = check_instances(instances)
     if inst is not None:
         mode.needs_mask("instances", "split")
-        if vec is None and not instances_raster:
+        if vec is None and not instances_raster and zones is None:
             raise ValueError("instances without an output: ask for the vector file, the instance raster or both")
-    if not return_array and not raster and vec is None:
+    zonal = check_zones(zones, zonal_objects)
+    if zonal:
+        mode.needs_mask("zonal statistics", "summarised")
+    if not return_array and not raster and vec is None and not zonal:
         raise ValueError("return_array=False needs out_path: the prediction would go nowhere")
     return dataclasses.replace(mode, blend=blend, postprocess=post, compress=compress, predictor=predictor, tile=tile, overviews=overviews,
-                               vector=vec, vector_simplify=vector_simplify, instances=inst, instances_raster=bool(instances_raster))
+                               vector=vec, vector_simplify=vector_simplify, instances=inst, instances_raster=bool(instances_raster),
+                               zones=zonal, zonal_objects=bool(zonal_objects))
 
 
-def _write_outputs(plan: OutputPlan, out, device, gt, tags, raster_path, vector_path, instances_path, class_names, timing):
+def _write_outputs(plan: OutputPlan, out, device, gt, tags, raster_path, vector_path, instances_path, class_names, timing, zones_path=None,
+                   zonal_path=None):
     """Rank 0's output stage on the merged array `out` of _Merge.finish (a tensor under plan.keep, else a NumPy array): the instance split (its
     dense ids as a uint32 GeoTIFF with the mask's geo tags, by tiffio.write_tiff, so compress, predictor and tile apply to it as to the mask),
-    the vector file, the move to the host unless the raster is encoded from the tensor, the raster.  Returns what the raster is written from."""
+    the vector file, the zonal table (its objects are the instances where there are any, else the components), the move to the host unless
+    the raster is encoded from the tensor, the raster.  Returns what the raster is written from."""
     labels = ids = None
     if plan.instances is not None:
         out = torch.as_tensor(out)
@@ -177,6 +189,10 @@ def _write_outputs(plan: OutputPlan, out, device, gt, tags, raster_path, vector_
                 timing.update(instances_write_seconds=time.perf_counter() - t0, instances_file_bytes=os.path.getsize(instances_path))
     if plan.vector is not None:
         vectorize_mask(out, vector_path, plan.vector, gt, epsg_of_tags(tags), class_names, plan.class_zero, timing, plan.vector_simplify, labels, ids)
+    if plan.zones:
+        out = torch.as_tensor(out)
+        out = (out if out.is_cuda else out.to(device)).contiguous()
+        zonal_mask(out, zones_path, zonal_path, gt, tags, class_names, plan.class_zero, labels, plan.zonal_objects, timing)
     if not plan.encode_in_place and isinstance(out, torch.Tensor):
         out = out.cpu().numpy()
     if raster_path is not None:
@@ -453,7 +469,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                    batch_size: int = 16, out_path=None, class_zero: bool = False, timing: Optional[dict] = None,
                    batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
                    return_array: bool = True, tile=None, overviews=None, vector_path=None, vector_exclude=None, vector_simplify=None,
-                   instances=None, instances_path=None):
+                   instances=None, instances_path=None, zones_path=None, zonal_path=None, zonal_objects: bool = False):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -504,12 +520,23 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
              id of the instance raster (0 for components of classes that are not split).  timing gains instances_seconds and instances
     instances_path  None | path of a uint32 GeoTIFF (needs instances): a dense id 1..N, in ascending label order, on every pixel of a
              split class and 0 elsewhere, with the geo tags of the mask; compress, predictor and tile apply to it (host encoder)
+    zones_path / zonal_path  None | the path of a GeoJSON file of Polygon / MultiPolygon zones in the raster's coordinates, and the path of the
+             table to write (.geojson: the zones with their geometry and properties; .csv: one row per zone); both or neither (ValueError).
+             The zones are burnt onto the output grid on the device (the rasterizer's rules: pixel centre, even-odd, the last zone wins) and
+             the pixels of every class per zone are counted there (unet_amd/zonal.py: pixels, area, px_<class>, frac_<class>, majority per
+             zone); only for the class mask and not with large_file (ValueError); a zones file whose EPSG code differs from the raster's
+             is refused (no reprojection).  timing gains zonal_seconds, zonal_zones and zonal_pixels
+    zonal_objects  True (needs zones_path): also n_<class>, the objects per zone and class -- the instances with instances=, else the
+             4-connected components; an object counts in the zone that holds its first pixel in row-major order
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
+    if (zones_path is None) != (zonal_path is None):
+        raise ValueError("zones_path and zonal_path go together: the zones to read and the table to write")
     plan = check_outputs(regression, all_classes, specific_class, large_file, True, class_zero, blend, postprocess, compress, predictor, tile,
                          overviews, vector_path, vector_exclude, vector_simplify, instances, instances_raster=instances_path is not None,
-                         raster=out_path is not None, return_array=return_array, raster_arg="instances_path")
+                         raster=out_path is not None, return_array=return_array, raster_arg="instances_path", zones=zones_path,
+                         zonal_objects=zonal_objects)
     model = getattr(model, "model", model)
     codes = tta_codes(tta, [(size, size)])
     rank, _, world = _dist_ctx()
@@ -553,7 +580,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                          plan.blend, plan.postprocess, plan.keep)
     if rank == 0:
         ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
-        out = _write_outputs(plan, out, dev, ogt, tags, out_path, vector_path, instances_path, None, timing)
+        out = _write_outputs(plan, out, dev, ogt, tags, out_path, vector_path, instances_path, None, timing, zones_path, zonal_path)
     if timing is not None:
         timing.update(kept_windows=len(wins), all_windows=int(len(keep)), mosaic=(MH, MW))
     if rank != 0 or not return_array:
@@ -713,7 +740,7 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
                      AOI=None, year=None, validation_vision=True, class_zero=False, batch_size=16, timing: Optional[dict] = None,
                      batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
                      tile=None, overviews=None, vector: bool = False, vector_exclude=None, vector_simplify=None, instances=None,
-                     instances_raster: bool = False):
+                     instances_raster: bool = False, zones=None, zonal_objects: bool = False):
     """tta, blend, postprocess, compress / predictor, tile / overviews, vector_exclude, vector_simplify and instances are predict_raster's (see
     there); the ValueErrors of check_outputs come before the model is loaded.  What differs here: tta applies to merged and per-tile outputs
     alike; blend, postprocess, vector and instances need merge=True (per-tile outputs: no overlap to blend, not post-processed, polygonized, split).
@@ -721,10 +748,12 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     (merge=False) use the host encoder.  tile / overviews: of the MERGED raster only; per-tile outputs ignore them, as a tile is one block anyway.
     vector (predict_raster's vector_path): True writes <merged raster stem>.geojson beside the merged raster, with the class names of the
     model's vocab.  instances_raster (predict_raster's instances_path): True writes <merged raster stem>_instances.tif beside it; instances
-    needs vector=True, instances_raster=True or both.
+    needs vector=True, instances_raster=True, zones or any of them.  zones (predict_raster's zones_path, with zonal_objects): the path of the
+    zones file; the table is written as <merged raster stem>_zonal.geojson beside the merged raster, with the class names of the vocab.
     validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
     plan = check_outputs(regression, all_classes, specific_class, large_file, merge, class_zero, blend, postprocess, compress, predictor, tile,
-                         overviews, vector or None, vector_exclude, vector_simplify, instances, instances_raster)
+                         overviews, vector or None, vector_exclude, vector_simplify, instances, instances_raster, zones=zones,
+                         zonal_objects=zonal_objects)
     rank, local_rank, world = _dist_ctx()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model
@@ -755,10 +784,11 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     if rank != 0:
         return None
     name = "_".join(filter(None, [AOI, year, model_name, "prediction"])) + ".tif"
-    vocab = getattr(learn.dls, "vocab", None) if plan.vector is not None else None
+    vocab = getattr(learn.dls, "vocab", None) if plan.vector is not None or plan.zones else None
     names = list(vocab) if vocab is not None and len(vocab) >= model.n_out else None
     _write_outputs(plan, out, model._device, gt, geos[0][1], output_folder / name, (output_folder / name).with_suffix(".geojson"),
-                   output_folder / (Path(name).stem + "_instances.tif") if plan.instances_raster else None, names, timing)
+                   output_folder / (Path(name).stem + "_instances.tif") if plan.instances_raster else None, names, timing,
+                   zones, output_folder / (Path(name).stem + "_zonal.geojson") if plan.zones else None)
     print(f"Prediction stored in {output_folder}.")
     return output_folder if regression else output_folder / name
 

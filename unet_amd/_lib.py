@@ -294,6 +294,9 @@ _sig = {
     "unet_ras_emit": (i, [vp, vp, vp, vp, ll, ll, i, i, vp, ll, vp, vp]),
     "unet_ras_spans": (i, [vp, ll, vp, ll, i, i, vp, vp, vp]),
     "unet_ras_resolve": (i, [vp, i, i, i, i, vp, vp]),
+    "unet_ras_resolve_ids": (i, [vp, i, i, vp, vp]),
+    "unet_zonal_lds_bins": (i, []),
+    "unet_zonal_counts": (i, [vp, vp, vp, i, i, i, i, vp, vp, vp, vp]),
 }
 # bf16-storage twins: same argument lists (every tensor is a void pointer on this side)
 for _n in ("bn_stats", "affine_act", "bn_bwd_reduce", "bn_bwd_apply", "maxpool3x3s2", "maxpool3x3s2_bwd", "avgpool2_ceil",

@@ -5,6 +5,7 @@
 //   unet_ras_emit      per edge: its crossings as keys feature << 40 | row << 20 | k, k = the first column whose centre lies at or right of it
 //   unet_ras_spans     sorted keys 2j, 2j + 1 bound one span of one (feature, row): atomicMax of (feature + 1) << 8 | value into the plane
 //   unet_ras_resolve   out = word ? word & 255 : (what out held, or fill)
+//   unet_ras_resolve_ids  ids = word ? (word >> 8) - 1 : -1: the feature that owns the pixel (unet_amd/zonal.py)
 // The sort between emit and spans is the caller's (one torch.sort).  Every position a kernel writes is computed (the scan) or clamped
 // (rows to 0 .. H - 1, columns to 0 .. W) and compared with the size of its buffer; the only atomic is a maximum of integers, which does
 // not depend on the order of arrival.
@@ -255,6 +256,22 @@ __global__ __launch_bounds__(256) void ras_resolve_kernel(const unsigned* __rest
     }
 }
 
+__device__ __forceinline__ int id_of(unsigned w) { return w ? (int)(w >> 8) - 1 : -1; }
+
+// 4 pixels per thread: one 16-byte load of the plane, one 16-byte store of ids
+__global__ __launch_bounds__(256) void ras_resolve_ids_kernel(const unsigned* __restrict__ plane, long long n, int vec, int* __restrict__ ids) {
+    const long long groups = (n + 3) / 4;
+    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long long)gridDim.x * 256) {
+        const long long i0 = g * 4;
+        if (vec && i0 + 4 <= n) {
+            const uint4 p = *reinterpret_cast<const uint4*>(plane + i0);
+            *reinterpret_cast<int4*>(ids + i0) = make_int4(id_of(p.x), id_of(p.y), id_of(p.z), id_of(p.w));
+        } else {
+            for (long long i = i0; i < i0 + 4 && i < n; ++i) ids[i] = id_of(plane[i]);
+        }
+    }
+}
+
 bool side_ok(int H, int W) { return H >= 1 && W >= 1 && H < RAS_MAX_SIDE && W < RAS_MAX_SIDE; }
 bool count_ok(long long v) { return v >= 1 && v <= RAS_MAX_COUNT; }
 bool aligned8(const void* p) { return (((uintptr_t)p) & 7) == 0; }
@@ -327,6 +344,16 @@ extern "C" int unet_ras_resolve(const uint32_t* plane, int H, int W, int fill, i
     const int vec = aligned16(plane) && aligned16(out) ? 1 : 0;
     hipLaunchKernelGGL(ras_resolve_kernel, dim3(ew_grid((n + 15) / 16, 256)), dim3(256), 0, (hipStream_t)stream, plane, n, (unsigned)fill, keep ? 1 : 0,
                        vec, out);
+    UNET_CHECK_LAUNCH();
+    return UNET_OK;
+}
+
+extern "C" int unet_ras_resolve_ids(const uint32_t* plane, int H, int W, int32_t* ids, void* stream) {
+    UNET_CHECK_ARG(plane && ids, "ras_resolve_ids: null pointer");
+    UNET_CHECK_ARG(side_ok(H, W), "ras_resolve_ids: H, W must be in 1..2^20 - 1 (got %d x %d)", H, W);
+    const long long n = (long long)H * W;
+    const int vec = aligned16(plane) && aligned16(ids) ? 1 : 0;
+    hipLaunchKernelGGL(ras_resolve_ids_kernel, dim3(ew_grid((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, plane, n, vec, ids);
     UNET_CHECK_LAUNCH();
     return UNET_OK;
 }

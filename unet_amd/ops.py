@@ -1968,6 +1968,85 @@ def ras_resolve(plane: torch.Tensor, fill: int, keep: bool, out: torch.Tensor):
     check(lib.unet_ras_resolve(plane.data_ptr(), H, W, fill, int(bool(keep)), out.data_ptr(), _stream()), "ras_resolve")
 
 
+def _table_tensor(what: str, name: str, t, dtype, shape):
+    """type, shape and contiguity of one argument: refused for host tensors too (_on_one_device comes behind all of them)"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise ValueError(f"{what}: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous")
+
+
+def _on_one_device(what: str, tensors):
+    """every given tensor of [(name, tensor or None), ...] lives on the GPU, and on the first one's"""
+    first_name, first = tensors[0]
+    for name, t in tensors:
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{what}: {name} must live on the GPU, got device {t.device}")
+        if t is not None and t.device != first.device:
+            raise ValueError(f"{what}: {name} lives on {t.device}, {first_name} on {first.device}")
+
+
+def ras_resolve_ids(plane: torch.Tensor, ids: torch.Tensor):
+    """ids (int32 [H, W]) = the feature that owns each pixel of the priority plane of ras_spans, -1 where there is none"""
+    H, W = check_raster_shape("ras_resolve_ids", plane.shape if isinstance(plane, torch.Tensor) else ())
+    _table_tensor("ras_resolve_ids", "plane", plane, torch.int32, (H, W))
+    _table_tensor("ras_resolve_ids", "ids", ids, torch.int32, (H, W))
+    _on_one_device("ras_resolve_ids", [("plane", plane), ("ids", ids)])
+    check(lib.unet_ras_resolve_ids(plane.data_ptr(), H, W, ids.data_ptr(), _stream()), "ras_resolve_ids")
+
+
+# ---------------------------------------------------------------------------------------------- zonal statistics (csrc/zonal.hip)
+
+ZONAL_MAX_CLASSES = 256
+ZONAL_MAX_BINS = 2 ** 31         # Z * C < 2^31: a key zone * C + class fits an int32
+
+
+def zonal_lds_bins() -> int:
+    """the largest Z * C that zonal_counts takes in its LDS form (a table of uint32 bins per workgroup); anything larger adds to the
+    global tables directly"""
+    return int(lib.unet_zonal_lds_bins())
+
+
+def check_zonal_sizes(what: str, Z, C) -> tuple:
+    """(Z, C) with 1 <= Z < 2^23, 1 <= C <= 256 and Z * C < 2^31"""
+    for name, v in (("the number of zones", Z), ("the number of classes", C)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{what}: {name} must be an int, got {v!r}")
+    if not 1 <= C <= ZONAL_MAX_CLASSES:
+        raise ValueError(f"{what}: the number of classes must lie in 1..256, got {C}")
+    if Z * C >= ZONAL_MAX_BINS:
+        raise ValueError(f"{what}: zones x classes must stay under 2^31, got {Z} x {C}")
+    if not 1 <= Z < RAS_MAX_FEATURES:
+        raise ValueError(f"{what}: the number of zones must lie in 1..2^23 - 1, got {Z}")
+    return Z, C
+
+
+def zonal_counts(zones: torch.Tensor, mask: torch.Tensor, labels: Optional[torch.Tensor], Z: int, C: int, counts: torch.Tensor,
+                 objects: Optional[torch.Tensor], bad: torch.Tensor):
+    """counts[z, c] += the pixels with zones == z and mask == c; with labels (int32, labels[p] = the smallest linear index of the object
+    of p) objects[z, c] += the anchors labels[p] == p among them.  counts and objects (int64 [Z, C]) are zeroed BY THE CALLER; bad
+    (int64[1]) is reset and gains bit 0 for a mask value >= C and bit 1 for a zone outside -1 .. Z - 1 (such pixels are counted nowhere)"""
+    what = "zonal_counts"
+    H, W = check_raster_shape(what, zones.shape if isinstance(zones, torch.Tensor) else ())
+    check_zonal_sizes(what, Z, C)
+    if (labels is None) != (objects is None):
+        raise ValueError(f"{what}: labels and objects are given together or not at all")
+    if labels is not None and H * W > VEC_MAX_COUNT:
+        raise ValueError(f"{what}: int32 labels index at most 2^31 - 1 pixels, got {H} x {W}")
+    _table_tensor(what, "zones", zones, torch.int32, (H, W))
+    _table_tensor(what, "mask", mask, torch.uint8, (H, W))
+    _table_tensor(what, "counts", counts, torch.int64, (Z, C))
+    _table_tensor(what, "bad", bad, torch.int64, (1,))
+    if labels is not None:
+        _table_tensor(what, "labels", labels, torch.int32, (H, W))
+        _table_tensor(what, "objects", objects, torch.int64, (Z, C))
+    _on_one_device(what, [("zones", zones), ("mask", mask), ("labels", labels), ("counts", counts), ("objects", objects), ("bad", bad)])
+    check(lib.unet_zonal_counts(zones.data_ptr(), mask.data_ptr(), _p(labels), H, W, Z, C, counts.data_ptr(), _p(objects), bad.data_ptr(),
+                                _stream()), what)
+
+
 # ---------------------------------------------------------------------------------------------- GeoTIFF strips on the device (csrc/tiff_encode.hip)
 
 def tiff_lzw_cap(n: int) -> int:

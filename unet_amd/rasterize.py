@@ -154,24 +154,22 @@ def _check_out(out, H: int, W: int, dev) -> Optional[torch.Tensor]:
     return out
 
 
-def rasterize(rings_or_polygons, shape, fill: int = 0, out: Optional[torch.Tensor] = None, stages: Optional[dict] = None) -> torch.Tensor:
-    """uint8 [H, W] device tensor: the burn values of the features (Rings, or Polygons: rings_from_polygons) under the rules of the module
-    docstring, `fill` (0..255) where no feature covers a pixel.  Host Rings are uploaded.  out: a contiguous uint8 [H, W] device tensor that
-    is burnt into in place and returned; uncovered pixels keep what it held.  stages: a dict that receives the milliseconds of count, scan,
-    emit, sort, spans and resolve (this synchronises the device after each: for measurements only), and the counts `crossings`, `features`
-    and `pair_mismatch`."""
-    H, W = ops.check_raster_shape("rasterize", tuple(shape) if isinstance(shape, (tuple, list, torch.Size)) else shape)
-    if not _is_int(fill) or not 0 <= fill <= 255:
-        raise ValueError(f"fill must be an int in 0..255, got {fill!r}")
+def _device_rings(what: str, rings_or_polygons, device=None) -> Rings:
+    """checked Rings on the device: Polygons are converted, host Rings uploaded (to `device`, or the current one)"""
     rings = rings_from_polygons(rings_or_polygons) if isinstance(rings_or_polygons, Polygons) else rings_or_polygons
     check_rings(rings)
     if not torch.cuda.is_available():
-        raise ValueError("rasterize runs on the GPU and there is no device (it has no host fallback)")
+        raise ValueError(f"{what} runs on the GPU and there is no device (it has no host fallback)")
     if not rings.xy.is_cuda:
-        rings = rings.to(out.device if isinstance(out, torch.Tensor) and out.is_cuda else "cuda")
+        rings = rings.to(device if device is not None else "cuda")
+    return rings
+
+
+def _priority_plane(rings: Rings, H: int, W: int, st: _Stages):
+    """the count / scan / emit / sort / spans passes, shared by rasterize() and unet_amd.zonal.rasterize_ids(): (plane, M, wrong) with plane
+    the int32 [H, W] priority plane, (feature + 1) << 8 | value on every covered pixel and 0 elsewhere, M the crossings and wrong the
+    pair-mismatch word (0, or this raises)"""
     dev = rings.xy.device
-    out = _check_out(out, H, W, dev)
-    st = _Stages(stages)
     i32, i64 = torch.int32, torch.int64
     V, R, F = rings.n_vertices, rings.n_rings, rings.n_features
     xy, ring_start, values = rings.xy.contiguous(), rings.ring_start.contiguous(), rings.values.contiguous()
@@ -207,13 +205,29 @@ def rasterize(rings_or_polygons, shape, fill: int = 0, out: Optional[torch.Tenso
     st.mark("spans")
     if wrong:
         raise RuntimeError(f"rasterize: {wrong} pair(s) of sorted crossings do not belong to one feature and row")
+    return plane, M, wrong
+
+
+def rasterize(rings_or_polygons, shape, fill: int = 0, out: Optional[torch.Tensor] = None, stages: Optional[dict] = None) -> torch.Tensor:
+    """uint8 [H, W] device tensor: the burn values of the features (Rings, or Polygons: rings_from_polygons) under the rules of the module
+    docstring, `fill` (0..255) where no feature covers a pixel.  Host Rings are uploaded.  out: a contiguous uint8 [H, W] device tensor that
+    is burnt into in place and returned; uncovered pixels keep what it held.  stages: a dict that receives the milliseconds of count, scan,
+    emit, sort, spans and resolve (this synchronises the device after each: for measurements only), and the counts `crossings`, `features`
+    and `pair_mismatch`."""
+    H, W = ops.check_raster_shape("rasterize", tuple(shape) if isinstance(shape, (tuple, list, torch.Size)) else shape)
+    if not _is_int(fill) or not 0 <= fill <= 255:
+        raise ValueError(f"fill must be an int in 0..255, got {fill!r}")
+    rings = _device_rings("rasterize", rings_or_polygons, out.device if isinstance(out, torch.Tensor) and out.is_cuda else None)
+    out = _check_out(out, H, W, rings.xy.device)
+    st = _Stages(stages)
+    plane, M, wrong = _priority_plane(rings, H, W, st)
     keep = out is not None
     if out is None:
-        out = _alloc((H, W), torch.uint8, dev)
+        out = _alloc((H, W), torch.uint8, plane.device)
     ops.ras_resolve(plane, int(fill), keep, out)
     st.mark("resolve")
     if stages is not None:
-        stages.update(crossings=M, features=F, pair_mismatch=wrong)
+        stages.update(crossings=M, features=rings.n_features, pair_mismatch=wrong)
     return out
 
 
@@ -239,19 +253,20 @@ def _burn_value(props, attribute: str, class_zero: bool, index: int) -> int:
     return int(v) + (1 if class_zero else 0)
 
 
-def read_geojson(path, geotransform=None, attribute: str = "class", class_zero: bool = False) -> Rings:
-    """Rings (host tensors) of a FeatureCollection of Polygon and MultiPolygon geometries: one feature each, in file order, holding all rings
-    of all its parts, with the integer property `attribute` (0..255) as its burn value.  Features with a null geometry are skipped; any other
-    geometry type, a missing or non-integer attribute or one outside 0..255 raises ValueError naming the feature index.  class_zero adds 1
-    to the attribute (the inverse of write_geojson's class_zero, so the attribute must be 0..254).  geotransform: map coordinates become
-    pixel coordinates in float64; without one the coordinates are pixel coordinates.  Uses the json module only."""
-    check_geojson_args(geotransform)
+def _load_collection(path) -> dict:
     with open(os.fspath(path)) as f:
         doc = json.load(f)
     if not isinstance(doc, dict) or doc.get("type") != "FeatureCollection" or not isinstance(doc.get("features"), list):
         raise ValueError(f"{path}: expected a GeoJSON FeatureCollection")
-    pts, ring_len, ring_count, values = [], [], [], []
-    for index, feat in enumerate(doc["features"]):
+    return doc
+
+
+def _parse_features(features: list, geotransform, on_feature):
+    """the one ring parser of read_geojson and unet_amd.zonal.read_zones: (quantised vertices [V, 2] with repeated closing points dropped,
+    the vertices per ring, the rings per read feature).  on_feature(index, feature) is called for every Polygon / MultiPolygon feature in
+    file order, after its geometry type was accepted and before its rings are parsed; features with a null geometry are skipped."""
+    pts, ring_len, ring_count = [], [], []
+    for index, feat in enumerate(features):
         geom = feat.get("geometry") if isinstance(feat, dict) else None
         if geom is None:
             continue
@@ -262,7 +277,7 @@ def read_geojson(path, geotransform=None, attribute: str = "class", class_zero: 
             rings = [ring for part in geom.get("coordinates") for ring in part]
         else:
             raise ValueError(f"feature {index}: geometry type {kind!r} is not supported (Polygon and MultiPolygon are)")
-        values.append(_burn_value(feat.get("properties"), attribute, class_zero, index))
+        on_feature(index, feat)
         ring_count.append(len(rings))
         for ring in rings:
             try:
@@ -283,11 +298,28 @@ def read_geojson(path, geotransform=None, attribute: str = "class", class_zero: 
     closed = (length > 1) & (q[np.minimum(first, max(len(q) - 1, 0))] == q[np.maximum(last, 0)]).all(axis=1) if len(q) else np.zeros(len(ring_len), bool)
     keep = np.ones(len(q), dtype=bool)
     keep[last[closed]] = False
-    length = length - closed
-    return check_rings(Rings(torch.from_numpy(np.ascontiguousarray(q[keep])).reshape(-1, 2),
+    return q[keep], length - closed, ring_count
+
+
+def _host_rings(xy: np.ndarray, length, ring_count, values) -> Rings:
+    return check_rings(Rings(torch.from_numpy(np.ascontiguousarray(xy)).reshape(-1, 2),
                              torch.from_numpy(np.concatenate([[0], np.cumsum(length)]).astype(np.int64)),
                              torch.from_numpy(np.concatenate([[0], np.cumsum(ring_count)]).astype(np.int64)),
                              torch.from_numpy(np.asarray(values, dtype=np.uint8))))
+
+
+def read_geojson(path, geotransform=None, attribute: str = "class", class_zero: bool = False) -> Rings:
+    """Rings (host tensors) of a FeatureCollection of Polygon and MultiPolygon geometries: one feature each, in file order, holding all rings
+    of all its parts, with the integer property `attribute` (0..255) as its burn value.  Features with a null geometry are skipped; any other
+    geometry type, a missing or non-integer attribute or one outside 0..255 raises ValueError naming the feature index.  class_zero adds 1
+    to the attribute (the inverse of write_geojson's class_zero, so the attribute must be 0..254).  geotransform: map coordinates become
+    pixel coordinates in float64; without one the coordinates are pixel coordinates.  Uses the json module only."""
+    check_geojson_args(geotransform)
+    doc = _load_collection(path)
+    values = []
+    xy, length, ring_count = _parse_features(doc["features"], geotransform,
+                                             lambda index, feat: values.append(_burn_value(feat.get("properties"), attribute, class_zero, index)))
+    return _host_rings(xy, length, ring_count, values)
 
 
 def rasterize_geojson(path, shape, geotransform=None, attribute: str = "class", fill: int = 0, class_zero: bool = False) -> torch.Tensor:
