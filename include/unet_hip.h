@@ -917,6 +917,31 @@ int unet_zonal_lds_bins(void);
 int unet_zonal_counts(const int32_t* zones, const uint8_t* mask, const int32_t* labels, int H, int W, int Z, int C, long long* counts,
                       long long* objects, long long* bad, void* stream);
 
+/* ------------------------------------------------------ object attributes --
+ * A keyed reduction per object over a label image (csrc/objects.hip, unet_amd/objects.py, DESIGN 3.23, where the rules are).  mask is uint8
+ * [H, W], labels int32 [H, W] (labels[p] = the smallest linear index of the object of pixel p; p is an anchor iff labels[p] == p), 1 <= H, W
+ * < 2^20, H * W <= 2^31 - 1.  exclude8: the excluded classes, 256 bits as 8 words.  The P objects are the anchors of the other classes in
+ * ascending order; offs = unet_vec_scan of their marks (unet_inst_marks with the kept classes), so offs[L] is the index of the object with
+ * anchor L.
+ * obj_compact: label[offs[p]] = p and cls[offs[p]] = mask[p] at every marked p; indices outside 0 .. P - 1 are not written.
+ * obj_accumulate: sums (uint64 [P, 5]) = pixels, sum of columns, sum of rows, edges_v, edges_h of every object, bbox (int32 [P, 4]) = x0, y0,
+ *   x1, y1 half open; both are initialised here.  *bad is reset and gains bit 0 for a label outside 0 .. H * W - 1, bit 1 for
+ *   labels[labels[p]] != labels[p], bit 2 for mask[labels[p]] != mask[p]; such pixels are counted nowhere and nothing is stored outside the
+ *   tables.  P = 0 (sums, bbox may be null): the check alone.
+ * obj_point: point[k] = the pixel of object k that minimises ((x - cx)^2 + (y - cy)^2, y W + x), cx = sum_x / pixels, cy = sum_y / pixels
+ *   (floored), from the complete sums; key64 (uint64 [P]) is workspace; bad is the word of obj_accumulate on the same planes, which made
+ *   the check of the input: with a bit set the passes do nothing.  One pass where unet_obj_point_packed(H, W) (the squared distance
+ *   stays below 2^33 and packs with the index into 64 bits), two minimum passes otherwise.
+ * Every accumulation is an integer atomic add, minimum or maximum.  16-byte accesses where labels is 16-byte and mask 4-byte aligned; no
+ * access outside the H * W elements.  Bad arguments return -1 before any launch. */
+int unet_obj_point_packed(int H, int W);
+int unet_obj_compact(const uint8_t* mask, const uint8_t* mark, const int32_t* offs, long long n, long long P, int32_t* label, uint8_t* cls,
+                     void* stream);
+int unet_obj_accumulate(const uint8_t* mask, const int32_t* labels, const int32_t* offs, int H, int W, const uint32_t* exclude8, long long P,
+                        long long* sums, int32_t* bbox, long long* bad, void* stream);
+int unet_obj_point(const uint8_t* mask, const int32_t* labels, const int32_t* offs, int H, int W, const uint32_t* exclude8, long long P,
+                   const long long* sums, const long long* bad, long long* key64, int32_t* point, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,12 @@ INSTANCES_RASTER = False
 # number of objects (components, or the instances of INSTANCES) per zone and class; an object counts in the zone of its first pixel
 ZONES = None
 ZONAL_OBJECTS = False
+# attributes of every object of the merged class mask (merge = True, class output), measured on the GPU (unet_amd/objects.py): OBJECTS False |
+# True writes <merged raster stem>_objects.geojson, one point per object (component, or instance of INSTANCES) inside it, with pixels, area,
+# perimeter, centroid, bbox, diameter, compactness and on_edge -- a tree list with crown diameters; with VECTOR the polygons carry the same
+# attributes.  OBJECTS_EXCLUDE None | class id | list of class ids whose objects are not measured
+OBJECTS = False
+OBJECTS_EXCLUDE = None
 # a mask_path that ends in .geojson / .json holds polygons instead of a raster: Create_tiles burns them on the GPU onto the image's grid
 # (unet_amd/rasterize.py) with this integer property as the class id
 MASK_ATTRIBUTE = "class"
@@ -116,7 +122,7 @@ MASK_ATTRIBUTE = "class"
 def main():
     global large_file, specific_class, all_classes, transforms, VALID_SCENES, self_attention, monitor, loss_func, LR_FINDER
     global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS
-    global VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY, INSTANCES, INSTANCES_RASTER, ZONES, ZONAL_OBJECTS
+    global VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY, INSTANCES, INSTANCES_RASTER, ZONES, ZONAL_OBJECTS, OBJECTS, OBJECTS_EXCLUDE
     t0 = time.time()
     if enable_extra_parameters:          # params_and_main.py:129-145
         import warnings
@@ -130,6 +136,7 @@ def main():
         VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY = False, None, None
         INSTANCES, INSTANCES_RASTER = None, False
         ZONES, ZONAL_OBJECTS = None, False
+        OBJECTS, OBJECTS_EXCLUDE = False, None
     if Create_tiles:
         from create_tiles_unet import split_raster
         split_raster(path_to_raster=image_path, path_to_mask=mask_path, base_dir=base_dir, patch_size=patch_size,
@@ -158,6 +165,8 @@ def main():
             extra["instances"], extra["instances_raster"] = INSTANCES, INSTANCES_RASTER
         if ZONES is not None:
             extra["zones"], extra["zonal_objects"] = ZONES, ZONAL_OBJECTS
+        if OBJECTS:
+            extra["objects"], extra["objects_exclude"] = True, OBJECTS_EXCLUDE
         save_predictions(predict_model, predict_path, regression, merge, all_classes, specific_class, large_file, AOI, year,
                          validation_vision, class_zero, tta=TTA, **extra)
     print(f"Operation completed in {(time.time() - t0) / 60:.2f} minutes.")

@@ -66,6 +66,7 @@ from unet_amd.tta import parse as tta_codes
 from unet_amd.vectorize import check_vector, epsg_of_tags, vectorize_mask
 from unet_amd.instances import Instances, check_instances
 from unet_amd.zonal import check_zones, zonal_mask
+from unet_amd.objects import check_objects, objects_mask
 
 
 def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_zero=False, compress=None, predictor=1,
@@ -116,6 +117,7 @@ class OutputPlan:
     instances_raster: bool = False
     zones: bool = False                               # a zonal table is written
     zonal_objects: bool = False
+    objects: Optional[tuple] = None                   # the classes that are not measured; None: no objects file
 
     mask = property(lambda p: not (p.regression or p.all_classes or p.specific_class is not None))       # the output is the class mask
     want = property(lambda p: 0 if p.regression else "all" if p.all_classes else "argmax" if p.mask else int(p.specific_class))    # _Merge.finish
@@ -124,7 +126,7 @@ class OutputPlan:
     nodata = property(lambda p: -9999 if p.regression else None)
     # a compressed raster is written from the tensor the merge assembled: on the device with one rank or RCCL, where only the bytes reach the host
     encode_in_place = property(lambda p: p.compress is not None and p.raster)
-    keep = property(lambda p: p.encode_in_place or p.vector is not None or p.instances is not None or p.zones)       # the merged array stays a tensor there
+    keep = property(lambda p: p.encode_in_place or p.vector is not None or p.instances is not None or p.zones or p.objects is not None)       # the merged array stays a tensor there
 
     def needs_mask(self, subject: str, done: str, one_device: bool = True):
         """the rule of every option that works on the class mask of a merged prediction"""
@@ -138,11 +140,11 @@ class OutputPlan:
 
 def check_outputs(regression=False, all_classes=False, specific_class=None, large_file=False, merge=True, class_zero=False, blend="mean",
                   postprocess=None, compress=None, predictor=1, tile=None, overviews=None, vector=None, vector_exclude=None, vector_simplify=None,
-                  instances=None, instances_raster=False, raster=True, return_array=True, raster_arg="instances_raster", zones=None,
-                  zonal_objects=False) -> OutputPlan:
+                  instances=None, instances_raster=False, raster=True, return_array=True, raster_arg="instances_raster", objects=None,
+                  objects_exclude=None, zones=None, zonal_objects=False) -> OutputPlan:
     """Every check of the two entry points' output arguments, from the arguments alone and in one order -> the OutputPlan.  vector: vector= or
     vector_path=; instances_raster: whether the argument named raster_arg asks for the instance raster; raster: whether out_path is given;
-    zones: zones= or zones_path= (the entry points check that its output path is there)"""
+    objects: objects= or objects_path=; zones: zones= or zones_path= (the entry points check that its output path is there)"""
     mode = OutputPlan(bool(regression), bool(all_classes), specific_class, bool(large_file), bool(merge), bool(class_zero), bool(raster))
     check_blend(blend, large_file, merge)
     post = check_postprocess(postprocess)
@@ -156,26 +158,30 @@ def check_outputs(regression=False, all_classes=False, specific_class=None, larg
         mode.needs_mask("a vector output", "polygonized")
     if instances is None and instances_raster:
         raise ValueError(f"{raster_arg} without instances")
+    obj = check_objects(objects, objects_exclude, class_zero)
+    if obj is not None:
+        mode.needs_mask("object attributes", "measured")
     inst = check_instances(instances)
     if inst is not None:
         mode.needs_mask("instances", "split")
-        if vec is None and not instances_raster and zones is None:
+        if vec is None and not instances_raster and zones is None and obj is None:
             raise ValueError("instances without an output: ask for the vector file, the instance raster or both")
     zonal = check_zones(zones, zonal_objects)
     if zonal:
         mode.needs_mask("zonal statistics", "summarised")
-    if not return_array and not raster and vec is None and not zonal:
+    if not return_array and not raster and vec is None and not zonal and obj is None:
         raise ValueError("return_array=False needs out_path: the prediction would go nowhere")
     return dataclasses.replace(mode, blend=blend, postprocess=post, compress=compress, predictor=predictor, tile=tile, overviews=overviews,
                                vector=vec, vector_simplify=vector_simplify, instances=inst, instances_raster=bool(instances_raster),
-                               zones=zonal, zonal_objects=bool(zonal_objects))
+                               zones=zonal, zonal_objects=bool(zonal_objects), objects=obj)
 
 
 def _write_outputs(plan: OutputPlan, out, device, gt, tags, raster_path, vector_path, instances_path, class_names, timing, zones_path=None,
-                   zonal_path=None):
+                   zonal_path=None, objects_path=None):
     """Rank 0's output stage on the merged array `out` of _Merge.finish (a tensor under plan.keep, else a NumPy array): the instance split (its
     dense ids as a uint32 GeoTIFF with the mask's geo tags, by tiffio.write_tiff, so compress, predictor and tile apply to it as to the mask),
-    the vector file, the zonal table (its objects are the instances where there are any, else the components), the move to the host unless
+    the object attributes (of the instances where there are any, else of the components; a vector file written too carries them on its
+    features), the vector file, the zonal table (its objects are the instances where there are any, else the components), the move to the host unless
     the raster is encoded from the tensor, the raster.  Returns what the raster is written from."""
     labels = ids = None
     if plan.instances is not None:
@@ -187,8 +193,15 @@ def _write_outputs(plan: OutputPlan, out, device, gt, tags, raster_path, vector_
             write_tiff(instances_path, ids.cpu().numpy().view(np.uint32), gt, tags, compress=plan.compress, predictor=plan.predictor, tile=plan.tile)
             if timing is not None:
                 timing.update(instances_write_seconds=time.perf_counter() - t0, instances_file_bytes=os.path.getsize(instances_path))
+    attributes = None
+    if plan.objects is not None:
+        out = torch.as_tensor(out)
+        out = (out if out.is_cuda else out.to(device)).contiguous()
+        attributes = objects_mask(out, objects_path, plan.objects, gt, epsg_of_tags(tags), class_names, plan.class_zero, labels, ids, timing)
     if plan.vector is not None:
-        vectorize_mask(out, vector_path, plan.vector, gt, epsg_of_tags(tags), class_names, plan.class_zero, timing, plan.vector_simplify, labels, ids)
+        extra = {} if attributes is None else {"attributes": attributes}          # without objects: the call it was
+        vectorize_mask(out, vector_path, plan.vector, gt, epsg_of_tags(tags), class_names, plan.class_zero, timing, plan.vector_simplify, labels, ids,
+                       **extra)
     if plan.zones:
         out = torch.as_tensor(out)
         out = (out if out.is_cuda else out.to(device)).contiguous()
@@ -469,7 +482,8 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                    batch_size: int = 16, out_path=None, class_zero: bool = False, timing: Optional[dict] = None,
                    batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
                    return_array: bool = True, tile=None, overviews=None, vector_path=None, vector_exclude=None, vector_simplify=None,
-                   instances=None, instances_path=None, zones_path=None, zonal_path=None, zonal_objects: bool = False):
+                   instances=None, instances_path=None, zones_path=None, zonal_path=None, zonal_objects: bool = False,
+                   objects_path=None, objects_exclude=None):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -528,6 +542,13 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
              is refused (no reprojection).  timing gains zonal_seconds, zonal_zones and zonal_pixels
     zonal_objects  True (needs zones_path): also n_<class>, the objects per zone and class -- the instances with instances=, else the
              4-connected components; an object counts in the zone that holds its first pixel in row-major order
+    objects_path  None | the path of a .geojson or .csv file: every object of the class mask (after postprocess) -- the instances with
+             instances=, else the 4-connected components -- is measured on the device (unet_amd/objects.py: pixels, area, perimeter,
+             centroid, bbox, diameter, compactness, on_edge and one representative pixel inside the object) and written as one Point
+             feature (or one row) per object in map coordinates; with vector_path the polygon features carry the same attributes.  Only
+             for the class mask and not with large_file (ValueError).  Under class_zero the NO_Data class 0 is not measured.  timing gains
+             objects_seconds and objects
+    objects_exclude  None | int | iterable of class ids (the model's, before the class_zero shift) whose objects are not measured
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
@@ -535,8 +556,8 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
         raise ValueError("zones_path and zonal_path go together: the zones to read and the table to write")
     plan = check_outputs(regression, all_classes, specific_class, large_file, True, class_zero, blend, postprocess, compress, predictor, tile,
                          overviews, vector_path, vector_exclude, vector_simplify, instances, instances_raster=instances_path is not None,
-                         raster=out_path is not None, return_array=return_array, raster_arg="instances_path", zones=zones_path,
-                         zonal_objects=zonal_objects)
+                         raster=out_path is not None, return_array=return_array, raster_arg="instances_path", objects=objects_path,
+                         objects_exclude=objects_exclude, zones=zones_path, zonal_objects=zonal_objects)
     model = getattr(model, "model", model)
     codes = tta_codes(tta, [(size, size)])
     rank, _, world = _dist_ctx()
@@ -580,7 +601,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                          plan.blend, plan.postprocess, plan.keep)
     if rank == 0:
         ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
-        out = _write_outputs(plan, out, dev, ogt, tags, out_path, vector_path, instances_path, None, timing, zones_path, zonal_path)
+        out = _write_outputs(plan, out, dev, ogt, tags, out_path, vector_path, instances_path, None, timing, zones_path, zonal_path, objects_path)
     if timing is not None:
         timing.update(kept_windows=len(wins), all_windows=int(len(keep)), mosaic=(MH, MW))
     if rank != 0 or not return_array:
@@ -740,7 +761,7 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
                      AOI=None, year=None, validation_vision=True, class_zero=False, batch_size=16, timing: Optional[dict] = None,
                      batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
                      tile=None, overviews=None, vector: bool = False, vector_exclude=None, vector_simplify=None, instances=None,
-                     instances_raster: bool = False, zones=None, zonal_objects: bool = False):
+                     instances_raster: bool = False, zones=None, zonal_objects: bool = False, objects: bool = False, objects_exclude=None):
     """tta, blend, postprocess, compress / predictor, tile / overviews, vector_exclude, vector_simplify and instances are predict_raster's (see
     there); the ValueErrors of check_outputs come before the model is loaded.  What differs here: tta applies to merged and per-tile outputs
     alike; blend, postprocess, vector and instances need merge=True (per-tile outputs: no overlap to blend, not post-processed, polygonized, split).
@@ -750,10 +771,12 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     model's vocab.  instances_raster (predict_raster's instances_path): True writes <merged raster stem>_instances.tif beside it; instances
     needs vector=True, instances_raster=True, zones or any of them.  zones (predict_raster's zones_path, with zonal_objects): the path of the
     zones file; the table is written as <merged raster stem>_zonal.geojson beside the merged raster, with the class names of the vocab.
+    objects (predict_raster's objects_path, with objects_exclude): True writes <merged raster stem>_objects.geojson beside the merged raster,
+    one Point feature per object with its attributes and the class names of the vocab; it counts as an output of instances.
     validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
     plan = check_outputs(regression, all_classes, specific_class, large_file, merge, class_zero, blend, postprocess, compress, predictor, tile,
-                         overviews, vector or None, vector_exclude, vector_simplify, instances, instances_raster, zones=zones,
-                         zonal_objects=zonal_objects)
+                         overviews, vector or None, vector_exclude, vector_simplify, instances, instances_raster, objects=objects or None,
+                         objects_exclude=objects_exclude, zones=zones, zonal_objects=zonal_objects)
     rank, local_rank, world = _dist_ctx()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model
@@ -784,11 +807,12 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     if rank != 0:
         return None
     name = "_".join(filter(None, [AOI, year, model_name, "prediction"])) + ".tif"
-    vocab = getattr(learn.dls, "vocab", None) if plan.vector is not None or plan.zones else None
+    vocab = getattr(learn.dls, "vocab", None) if plan.vector is not None or plan.zones or plan.objects is not None else None
     names = list(vocab) if vocab is not None and len(vocab) >= model.n_out else None
     _write_outputs(plan, out, model._device, gt, geos[0][1], output_folder / name, (output_folder / name).with_suffix(".geojson"),
                    output_folder / (Path(name).stem + "_instances.tif") if plan.instances_raster else None, names, timing,
-                   zones, output_folder / (Path(name).stem + "_zonal.geojson") if plan.zones else None)
+                   zones, output_folder / (Path(name).stem + "_zonal.geojson") if plan.zones else None,
+                   output_folder / (Path(name).stem + "_objects.geojson") if plan.objects is not None else None)
     print(f"Prediction stored in {output_folder}.")
     return output_folder if regression else output_folder / name
 

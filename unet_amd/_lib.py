@@ -297,6 +297,10 @@ _sig = {
     "unet_ras_resolve_ids": (i, [vp, i, i, vp, vp]),
     "unet_zonal_lds_bins": (i, []),
     "unet_zonal_counts": (i, [vp, vp, vp, i, i, i, i, vp, vp, vp, vp]),
+    "unet_obj_point_packed": (i, [i, i]),
+    "unet_obj_compact": (i, [vp, vp, vp, ll, ll, vp, vp, vp]),
+    "unet_obj_accumulate": (i, [vp, vp, vp, i, i, C.POINTER(C.c_uint32), ll, vp, vp, vp, vp]),
+    "unet_obj_point": (i, [vp, vp, vp, i, i, C.POINTER(C.c_uint32), ll, vp, vp, vp, vp, vp]),
 }
 # bf16-storage twins: same argument lists (every tensor is a void pointer on this side)
 for _n in ("bn_stats", "affine_act", "bn_bwd_reduce", "bn_bwd_apply", "maxpool3x3s2", "maxpool3x3s2_bwd", "avgpool2_ceil",

@@ -2047,6 +2047,87 @@ def zonal_counts(zones: torch.Tensor, mask: torch.Tensor, labels: Optional[torch
                                 _stream()), what)
 
 
+# ---------------------------------------------------------------------------------------------- object attributes (csrc/objects.hip)
+
+def check_objects_shape(what: str, shape) -> tuple:
+    """(H, W) within check_raster_shape and H * W <= 2^31 - 1 (int32 labels index the pixels)"""
+    H, W = check_raster_shape(what, shape)
+    if H * W > VEC_MAX_COUNT:
+        raise ValueError(f"{what}: int32 labels index at most 2^31 - 1 pixels, got {H} x {W}")
+    return H, W
+
+
+def obj_point_packed(H: int, W: int) -> bool:
+    """whether obj_point finds the representative pixels of an H x W raster in one pass: (H - 1)^2 + (W - 1)^2 < 2^33, so that the squared
+    distance and the 31-bit index share one 64-bit key"""
+    return bool(lib.unet_obj_point_packed(int(H), int(W)))
+
+
+def _obj_planes(what: str, mask, labels, offs) -> tuple:
+    H, W = check_objects_shape(what, mask.shape if isinstance(mask, torch.Tensor) else ())
+    _table_tensor(what, "mask", mask, torch.uint8, (H, W))
+    _table_tensor(what, "labels", labels, torch.int32, (H, W))
+    _table_tensor(what, "offs", offs, torch.int32, (H, W))
+    return H, W
+
+
+def _obj_count(what: str, P, n: int, least: int) -> int:
+    if isinstance(P, bool) or not isinstance(P, int) or not least <= P <= n:
+        raise ValueError(f"{what}: P must be an int in {least}..H * W, got {P!r}")
+    return P
+
+
+def obj_compact(mask: torch.Tensor, mark: torch.Tensor, offs: torch.Tensor, P: int, label: torch.Tensor, cls: torch.Tensor):
+    """label[offs[p]] = p and cls[offs[p]] = mask[p] at every p with mark[p] != 0 (mark uint8 [H, W], offs = vec_scan(mark), P its total)"""
+    what = "obj_compact"
+    H, W = check_objects_shape(what, mask.shape if isinstance(mask, torch.Tensor) else ())
+    _obj_count(what, P, H * W, 1)
+    _table_tensor(what, "mask", mask, torch.uint8, (H, W))
+    _table_tensor(what, "mark", mark, torch.uint8, (H, W))
+    _table_tensor(what, "offs", offs, torch.int32, (H, W))
+    _table_tensor(what, "label", label, torch.int32, (P,))
+    _table_tensor(what, "cls", cls, torch.uint8, (P,))
+    _on_one_device(what, [("mask", mask), ("mark", mark), ("offs", offs), ("label", label), ("cls", cls)])
+    check(lib.unet_obj_compact(mask.data_ptr(), mark.data_ptr(), offs.data_ptr(), H * W, P, label.data_ptr(), cls.data_ptr(), _stream()), what)
+
+
+def obj_accumulate(mask: torch.Tensor, labels: torch.Tensor, offs: torch.Tensor, exclude, P: int, sums: Optional[torch.Tensor],
+                   bbox: Optional[torch.Tensor], bad: torch.Tensor):
+    """sums (int64 [P, 5]: pixels, sum_x, sum_y, edges_v, edges_h) and bbox (int32 [P, 4]: x0, y0, x1, y1 half open) of the P objects whose
+    index is offs[anchor], both initialised by the call; bad (int64[1]) is reset and gains bit 0 for a label outside 0 .. H * W - 1, bit 1
+    for labels[labels[p]] != labels[p], bit 2 for mask[labels[p]] != mask[p].  P = 0 (sums, bbox None): the check of the input alone"""
+    what = "obj_accumulate"
+    H, W = _obj_planes(what, mask, labels, offs)
+    _obj_count(what, P, H * W, 0)
+    _table_tensor(what, "bad", bad, torch.int64, (1,))
+    if P:
+        _table_tensor(what, "sums", sums, torch.int64, (P, 5))
+        _table_tensor(what, "bbox", bbox, torch.int32, (P, 4))
+    elif sums is not None or bbox is not None:
+        raise ValueError(f"{what}: no tables without objects")
+    _on_one_device(what, [("mask", mask), ("labels", labels), ("offs", offs), ("sums", sums), ("bbox", bbox), ("bad", bad)])
+    words = (C.c_uint32 * 8)(*vec_exclude_words(exclude))
+    check(lib.unet_obj_accumulate(mask.data_ptr(), labels.data_ptr(), offs.data_ptr(), H, W, words, P, _p(sums), _p(bbox), bad.data_ptr(),
+                                  _stream()), what)
+
+
+def obj_point(mask: torch.Tensor, labels: torch.Tensor, offs: torch.Tensor, exclude, P: int, sums: torch.Tensor, bad: torch.Tensor,
+              key64: torch.Tensor, point: torch.Tensor):
+    """point (int32 [P]) = the representative pixel of every object from the complete sums of obj_accumulate; bad: the word of that call on
+    the same planes (it made the check of the input: with a bit set nothing is done); key64 (int64 [P]) is workspace"""
+    what = "obj_point"
+    H, W = _obj_planes(what, mask, labels, offs)
+    _obj_count(what, P, H * W, 1)
+    _table_tensor(what, "sums", sums, torch.int64, (P, 5))
+    _table_tensor(what, "bad", bad, torch.int64, (1,))
+    _table_tensor(what, "key64", key64, torch.int64, (P,))
+    _table_tensor(what, "point", point, torch.int32, (P,))
+    _on_one_device(what, [("mask", mask), ("labels", labels), ("offs", offs), ("sums", sums), ("bad", bad), ("key64", key64), ("point", point)])
+    words = (C.c_uint32 * 8)(*vec_exclude_words(exclude))
+    check(lib.unet_obj_point(mask.data_ptr(), labels.data_ptr(), offs.data_ptr(), H, W, words, P, sums.data_ptr(), bad.data_ptr(),
+                             key64.data_ptr(), point.data_ptr(), _stream()), what)
+
+
 # ---------------------------------------------------------------------------------------------- GeoTIFF strips on the device (csrc/tiff_encode.hip)
 
 def tiff_lzw_cap(n: int) -> int:

@@ -455,15 +455,22 @@ def check_geojson_args(geotransform=None, epsg=None):
         raise ValueError(f"epsg must be None or a positive int, got {epsg!r}")
 
 
-def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, codes=None, class_zero: bool = False, instance=None) -> int:
+ATTRIBUTE_KEYS = ("perimeter", "centroid_x", "centroid_y", "diameter", "compactness", "on_edge", "point_x", "point_y")
+
+
+def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, codes=None, class_zero: bool = False, instance=None,
+                  attributes=None) -> int:
     """One FeatureCollection with one Polygon feature per component, in poly_label order: the exterior ring, then the holes, each closed by
     repeating its first point.  Coordinates are X = gt[0] + x gt[1], Y = gt[3] + y gt[5] in float64, written with repr; integer pixel
     coordinates without a geotransform.  Properties: class (the id as the raster on disk holds it: class - 1 under class_zero, where
     class 0 -- NO_Data -- gets no feature), name (codes[class], if codes are given), pixels, area (pixels |gt[1] gt[5]|).  With an EPSG code
     the legacy "crs" member names urn:ogc:def:crs:EPSG::<code>.  instance: None, or one id per polygon, written as the property `instance`
-    behind the others.  Returns the number of features.  Host code."""
+    behind the others.  attributes: None, or a mapping from a polygon's label to its row of unet_amd/objects.object_rows; a feature whose label
+    has a row gains the ATTRIBUTE_KEYS of that row behind its other properties (joined by label: with a simplification some polygons get
+    no feature).  Returns the number of features.  Host code."""
     check_geojson_args(geotransform, epsg)
     a = _host_arrays(polys)
+    labels = a["poly_label"].tolist() if attributes is not None else None
     gt = None if geotransform is None else tuple(float(v) for v in geotransform)
     xy = a["xy"].astype(np.int64)
     if gt is None:
@@ -489,6 +496,9 @@ def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, co
         props["area"] = pixels * px_area
         if inst is not None:
             props["instance"] = int(inst[i])
+        row = attributes.get(labels[i]) if attributes is not None else None
+        if row is not None:
+            props.update((k, row[k]) for k in ATTRIBUTE_KEYS)
         coords = ",".join("[" + ",".join(pts[rs[r]:rs[r + 1]] + pts[rs[r]:rs[r] + 1]) + "]" for r in rings[prs[i]:prs[i + 1]])
         feats.append('{"type":"Feature","properties":' + json.dumps(props) + ',"geometry":{"type":"Polygon","coordinates":[' + coords + "]}}")
     head = '{"type":"FeatureCollection",'
@@ -517,18 +527,19 @@ def check_vector(vector, vector_exclude=None, class_zero: bool = False, simplify
 
 
 def vectorize_mask(mask, path, exclude=(), geotransform=None, epsg=None, codes=None, class_zero: bool = False, timing: Optional[dict] = None,
-                   simplify=None, labels=None, ids=None) -> Polygons:
+                   simplify=None, labels=None, ids=None, attributes=None) -> Polygons:
     """polygonize + write_geojson of an assembled class mask (device or host); timing gains vector_seconds / _polygons / _vertices and
     vector_vertices_raw (the vertices before the simplification; equal to vector_vertices without one).  labels / ids (device tensors of
     unet_amd/instances.py: the instance labels and their dense ids per pixel): one feature per instance, with the id of its pixels as the
-    property `instance` (0 for the components of a class that is not split)"""
+    property `instance` (0 for the components of a class that is not split).  attributes: as in write_geojson"""
     t0 = time.perf_counter()
     if labels is None:
         polys = polygonize(mask, exclude, simplify)
-        n = write_geojson(path, polys, geotransform, epsg, codes, class_zero)
+        n = write_geojson(path, polys, geotransform, epsg, codes, class_zero, attributes=attributes)
     else:
         polys = polygonize_labels(mask, labels, exclude, simplify)
-        n = write_geojson(path, polys, geotransform, epsg, codes, class_zero, instance=ids.view(-1)[polys.poly_label.to(torch.int64)])
+        n = write_geojson(path, polys, geotransform, epsg, codes, class_zero, instance=ids.view(-1)[polys.poly_label.to(torch.int64)],
+                          attributes=attributes)
     if timing is not None:
         timing.update(vector_seconds=time.perf_counter() - t0, vector_polygons=n, vector_vertices=polys.n_vertices,
                       vector_vertices_raw=polys.n_vertices if simplify is None else polys.raw_vertices)
