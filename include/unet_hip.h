@@ -697,6 +697,26 @@ int unet_border_edt(const void* mask, int mask_is_int64, int B, int H, int W, in
 int unet_border_weight(const int32_t* d2, const int64_t* target, const float* class_w, int C, float w0, double sigma, long long P,
                        float* pw, void* stream);
 
+/* ------------------------------------------- distance to the two nearest objects --
+ * csrc/object_edt.hip (unet_amd/border.py).  Masks as above, with B * H * W <= 2^31 - 1.  A pixel is EXCLUDED when its value
+ * equals exclude (-1: none) or lies outside [0, n_classes) (n_classes 1..256), BACKGROUND when it is not excluded and equals background
+ * (0..255, != exclude), and an OBJECT pixel otherwise; an object is a 4-connected component of object pixels of one value in one image.
+ * unet_object_edt: for a background pixel p, d1 / d2 int32 [B, H, W] = the smallest and the second smallest of delta(p, L) = min over the
+ *   pixels q of object L of |p - q|^2 over the distinct objects L with delta <= radius^2 (radius 1..255); INT32_MAX where there is no
+ *   such object and at object and excluded pixels.  pw float [B, H, W] = class_w[y] + w0 * exp(-(sqrt d1 + sqrt d2)^2 / (2 sigma^2)) with
+ *   the exponent formed in fp64 as d1 + d2 + 2 sqrt(d1 d2) and rounded to fp32 once; class_w [n_classes] or NULL (ones); the second term
+ *   is exactly 0 where d2 is INT32_MAX; a value outside [0, n_classes) gives 0.  d1 and d2 (both or neither) and pw may be NULL, not all.
+ *   Launches: the key image (image << 8 | value for object pixels, a key of its own for every other pixel), unet_cc_label_keys on the
+ *   stacked [B * H, W] key image, a column pass (per pixel the two nearest object pixels of its column with distinct labels within
+ *   radius rows of the same image) and a row pass with the candidates of radius columns either side in LDS.  Integers only in the
+ *   distances, no atomics outside the labelling, one thread per output: independent of the schedule.  No host sync; capturable.
+ *   The workspace (unet_object_edt_workspace BYTES, 16-byte aligned, the caller's) holds keys, labels, candidates and the labelling's
+ *   counters: 18 bytes per pixel.
+ * Bad arguments return -1 before any launch. */
+size_t unet_object_edt_workspace(int B, int H, int W);   /* bytes; 0 for a shape outside the limits */
+int unet_object_edt(const void* mask, int mask_is_int64, int B, int H, int W, int background, int exclude, int n_classes, int radius,
+                    void* workspace, int32_t* d1, int32_t* d2, const float* class_w, float w0, double sigma, float* pw, void* stream);
+
 /* ------------------------------------------------------ GeoTIFF codecs --
  * Host-side (no device code) strip / tile decoders of unet_amd/tiffio.py.  Replaces what GDAL / rasterio do when the reference opens a
  * compressed raster (create_tiles_unet.py:252-434: gdal.Open / ReadAsArray; data.py:18-28: rasterio.open().read()).  Deflate is zlib.

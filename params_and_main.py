@@ -56,6 +56,8 @@ loss_func = None               # None = CrossEntropyLossFlat(axis=1) (the refere
                                # regression: MSELossFlat(axis=1), L1LossFlat
                                # BorderWeightedCrossEntropy(axis=1, w0=10, sigma=5, exclude=None): the U-Net paper's cross-entropy with a per-pixel
                                # weight that is large near class borders (thin gaps between crowns, roofs, parcels); exclude=0 with class_zero
+                               # LOSS_FUNCTION (loss_func here) = BorderWeightedCrossEntropy(objects=True): the paper's own (d1 + d2) form -- the weight is large only
+                               # on background pixels between two different objects (background=0, radius=None = ceil(6 sigma) px)
 monitor = "valid_loss"         # 'dice_multi', 'r2_score', 'train_loss', 'valid_loss'
 all_classes = False
 specific_class = None

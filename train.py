@@ -104,6 +104,8 @@ def train_unet(class_weights, dls, architecture, epochs, path, lr, encoder_facto
     else:
         if loss_func is None:
             loss_func = CrossEntropyLossFlat(axis=1, weight=weights)
+        # params_and_main.py, LOSS_FUNCTION = BorderWeightedCrossEntropy(objects=True): the U-Net paper's (d1 + d2) weight, large only in the
+        # gap between two objects; the class weights arrive through .func.weight below like every loss's
         metrics = [DiceMulti()]
     monitor = monitor or ("r2_score" if regression else "dice_multi")
     comp = np.less if monitor in ("train_loss", "valid_loss") else np.greater

@@ -258,6 +258,8 @@ _sig = {
     "unet_edt_workspace": (sz, [i, i, i]),
     "unet_border_edt": (i, [vp, i, i, i, i, i, vp, vp, vp]),
     "unet_border_weight": (i, [vp, vp, vp, i, f, C.c_double, ll, vp, vp]),
+    "unet_object_edt_workspace": (sz, [i, i, i]),
+    "unet_object_edt": (i, [vp, i, i, i, i, i, i, i, i, vp, vp, vp, vp, f, C.c_double, vp, vp]),
     "unet_vec_flags": (i, [vp, vp, i, i, C.POINTER(C.c_uint32), vp, vp]),
     "unet_vec_scan_words": (ll, [ll]),
     "unet_vec_scan": (i, [vp, ll, vp, vp, vp]),

@@ -9,8 +9,8 @@ train_bn, moms`` (``train.py:148-154``); ``unfreeze`` (``:246``); ``fit_one_cycl
 ``get_preds``; ``summary``; callbacks ``SaveModelCallback(monitor, comp, fname)`` and ``CSVLogger`` (``train.py:209``);
 ``CrossEntropyLossFlat(axis=1, weight)`` with assignable ``.func.weight`` (``train.py:195,211``), ``FocalLossFlat(gamma, axis=1)``
 (``params_and_main.py:87-89``), ``DiceLoss(axis=1, smooth, reduction, square_in_union)``, ``CombinedLoss(axis=1, smooth, alpha)`` (focal +
-alpha * Dice, from fastai's documentation of DiceLoss), ``BorderWeightedCrossEntropy(axis=1, weight, w0, sigma, exclude)`` (the U-Net
-paper's border-weighted cross-entropy); ``DiceMulti``.
+alpha * Dice, from fastai's documentation of DiceLoss), ``BorderWeightedCrossEntropy(axis=1, weight, w0, sigma, exclude, objects=,
+background=, radius=)`` (the U-Net paper's border-weighted cross-entropy, in the nearest-border or the two-object form); ``DiceMulti``.
 """
 from __future__ import annotations
 
@@ -105,14 +105,21 @@ class BorderWeightedCrossEntropy(CrossEntropyLossFlat):
     borders, ``w(p) = weight[y(p)] + w0 * exp(-d(p)^2 / (2 sigma^2))``, loss = ``sum w nll / sum w``.  ``d`` is the Euclidean distance to the
     nearest border pixel of the tile (unet_amd/border.py has the rules; ``exclude=0`` keeps edges against the NO_Data class out).  The map is
     taken from the mask the step sees, after augmentation, on the device.  ``w0=10, sigma=5`` are the paper's.  ``.func.weight`` (train.py:211
-    assigns it for every loss) is the class term.  The paper's two-instance form ``(d1 + d2)^2``, the distances to the two nearest OBJECTS, is
-    out of scope: this loss knows classes, not instances.  Fused on the device (unet_border_edt, unet_border_weight, unet_ce_fwd_pw /
-    unet_ce_bwd_pw)."""
+    assigns it for every loss) is the class term.  ``objects=True`` takes the paper's own two-object form instead,
+    ``w0 * exp(-(d1(p) + d2(p))^2 / (2 sigma^2))`` on the pixels of the ``background`` class, d1 and d2 the distances to the nearest and the
+    second nearest object (a 4-connected region of one class) within ``radius`` (None: ceil(6 sigma)): large only in the gap between two
+    objects; ``exclude`` then names a class that is neither background nor object.  Fused on the device (unet_border_edt,
+    unet_border_weight or unet_object_edt, unet_ce_fwd_pw / unet_ce_bwd_pw)."""
 
-    def __init__(self, axis: int = 1, weight: Optional[torch.Tensor] = None, w0: float = 10.0, sigma: float = 5.0, exclude: Optional[int] = None):
+    # read through the class by objects pickled before these existed: they behave as objects=False
+    objects, background, radius = False, 0, None
+
+    def __init__(self, axis: int = 1, weight: Optional[torch.Tensor] = None, w0: float = 10.0, sigma: float = 5.0, exclude: Optional[int] = None,
+                 *, objects: bool = False, background: int = 0, radius: Optional[int] = None):
         super().__init__(axis=axis, weight=weight)
-        from .border import check_border_params
+        from .border import check_border_params, check_object_params
         self.w0, self.sigma, self.exclude = check_border_params(w0, sigma, exclude)
+        self.objects, self.background, self.radius = check_object_params(self.sigma, objects, background, radius, self.exclude)
 
     def __call__(self, logits: torch.Tensor, targ: torch.Tensor) -> torch.Tensor:
         """Generic path (torch autograd): the same formula, the map from border_weight_map."""
@@ -120,7 +127,8 @@ class BorderWeightedCrossEntropy(CrossEntropyLossFlat):
         C = logits.shape[self.axis]
         targ = targ.long()
         w = self._w(targ.device)
-        pw = border_weight_map(targ, w, self.w0, self.sigma, self.exclude, n_classes=C).to(logits.device, logits.dtype)
+        pw = border_weight_map(targ, w, self.w0, self.sigma, self.exclude, n_classes=C, objects=self.objects, background=self.background,
+                               radius=self.radius).to(logits.device, logits.dtype)
         valid = (targ >= 0) & (targ < C)
         nll = torch.nn.functional.cross_entropy(logits, torch.where(valid, targ, -100), reduction="none")
         return (pw * nll).sum() / pw.sum()
@@ -1132,7 +1140,9 @@ class Learner:
                                  "square_in_union": cl.square_in_union,
                                  "class_weights": None if cl.func.weight is None else [float(v) for v in torch.as_tensor(cl.func.weight).cpu()]}}
                    if cl is not None else {}),
-                **({"border": {"w0": self._border.w0, "sigma": self._border.sigma, "exclude": self._border.exclude}}
+                **({"border": {"w0": self._border.w0, "sigma": self._border.sigma, "exclude": self._border.exclude,
+                               **({"objects": True, "background": self._border.background, "radius": self._border.radius}
+                                  if self._border.objects else {})}}
                    if self._border is not None else {}),
                 "self_attention": bool(getattr(m, "self_attention", False)), "act_dtype": getattr(m, "act_dtype", "f32")}
         p = Path(fname)
@@ -1191,5 +1201,6 @@ def _loss_from_meta(meta: dict):
     wt = None if w is None else torch.tensor(w)
     if meta.get("border") is not None:
         d = meta["border"]
-        return BorderWeightedCrossEntropy(axis=1, weight=wt, w0=d["w0"], sigma=d["sigma"], exclude=d["exclude"])
+        return BorderWeightedCrossEntropy(axis=1, weight=wt, w0=d["w0"], sigma=d["sigma"], exclude=d["exclude"], objects=d.get("objects", False),
+                                          background=d.get("background", 0), radius=d.get("radius"))
     return CrossEntropyLossFlat(axis=1, weight=wt) if meta.get("focal_gamma") is None else FocalLossFlat(gamma=meta["focal_gamma"], axis=1, weight=wt)

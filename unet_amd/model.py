@@ -465,9 +465,18 @@ class HipDynamicUnet(nn.Module):
 
     def border_weights(self, y: torch.Tensor, weight: Optional[torch.Tensor], border, n_classes: int) -> torch.Tensor:
         """float32 [P]: the border weight map of the int64 masks y [B, H, W] (unet_amd/border.py) in a persistent buffer of the context;
-        two C-ABI calls (three launches) on the current stream.  The distance transform's intermediate is the shared workspace."""
+        two C-ABI calls (three launches) on the current stream.  The distance transform's intermediate is the shared workspace.
+        border.objects set: the paper's two-object form instead, w0 * exp(-(d1 + d2)^2 / (2 sigma^2)) -- one C-ABI call (keys, three
+        labelling launches, column pass, row pass with the map fused) whose 18 bytes per pixel of keys, labels and candidates are the shared
+        workspace too; only the map itself is kept."""
         ctx = self.ctx
         B, H, W = (int(v) for v in y.shape)
+        if getattr(border, "objects", False):
+            from .border import object_radius
+            pw = ctx.vec(self, "border_pw", y.numel())
+            ops.object_border_weight(y, weight, n_classes, border.w0, border.sigma, pw, ctx.workspace((ops.object_edt_workspace(B, H, W) + 3) // 4),
+                                     getattr(border, "background", 0), border.exclude, object_radius(border.sigma, getattr(border, "radius", None)))
+            return pw
         d2 = ctx.vec(self, "border_d2", y.numel(), dtype=torch.int32)
         pw = ctx.vec(self, "border_pw", y.numel())
         ops.border_edt(y, d2, ctx.workspace((ops.edt_workspace(B, H, W) + 3) // 4), border.exclude)
@@ -497,7 +506,8 @@ class HipDynamicUnet(nn.Module):
         border: BorderWeightedCrossEntropy instead -- any object with .w0, .sigma and .exclude: the cross-entropy with one weight per pixel,
         weight[y] + w0 * exp(-D^2 / (2 sigma^2)), D the distance to the nearest class border of the tile (unet_amd/border.py).  Border distance,
         weight map, loss forward and backward are four C-ABI calls on the step's stream, no host sync.  A pixel's weight depends on its own
-        tile only, so the N-rank rule is the plain cross-entropy's: numerator and denominator all-reduced.
+        tile only, so the N-rank rule is the plain cross-entropy's: numerator and denominator all-reduced.  With border.objects the map is
+        the two-object one (border_weights); everything behind the map is the same.
         Regression (reg_kind = "mse" | "l1" | "smoothl1", n_out = 1, float targets [B,H,W]): train.py:189-193."""
         if border is not None:
             if dice is not None or combined is not None or focal_gamma is not None or reg_kind is not None:

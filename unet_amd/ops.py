@@ -2326,3 +2326,80 @@ def border_weight(d2: torch.Tensor, target: torch.Tensor, class_w, n_classes: in
         raise ValueError("border_weight: every tensor must live on one device")
     check(lib.unet_border_weight(d2.data_ptr(), target.data_ptr(), _p(class_w), n_classes, float(w0), float(sigma), P, pw.data_ptr(), _stream()),
           "border_weight")
+
+
+# ---------------------------------------------------------------------------------------------- two nearest objects (csrc/object_edt.hip)
+
+OBJ_MAX_RADIUS = 255
+OBJ_MAX_CLASSES = 256        # an object's value is one byte of its key
+OBJ_NO_OBJECT = 2 ** 31 - 1  # D1 / D2 where no object lies within the radius, and off the background
+
+
+def check_object_shape(what: str, shape):
+    """check_edt_shape and B * H * W <= 2^31 - 1 (a label is a linear index of the stacked batch)"""
+    check_edt_shape(what, shape)
+    if int(shape[0]) * int(shape[1]) * int(shape[2]) > 2 ** 31 - 1:
+        raise ValueError(f"{what}: {tuple(int(v) for v in shape)} holds more than 2^31 - 1 pixels")
+
+
+def _obj_int(what: str, name: str, v, lo: int, hi: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError(f"{what}: {name} must be an int in {lo}..{hi}, got {v!r}")
+    return v
+
+
+def object_edt_workspace(B: int, H: int, W: int) -> int:
+    """bytes of the workspace of object_edt / object_border_weight: keys, labels and two candidates per pixel, 18 bytes per pixel"""
+    check_object_shape("object_edt_workspace", (B, H, W))
+    return int(lib.unet_object_edt_workspace(B, H, W))
+
+
+def _object_call(what: str, mask, ws, background, exclude, n_classes, radius, d1, d2, class_w, w0, sigma, pw):
+    check_object_shape(what, getattr(mask, "shape", ()))
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.int64):
+        raise ValueError(f"{what}: mask must be a uint8 or int64 tensor, got {getattr(mask, 'dtype', type(mask))}")
+    if not mask.is_cuda or not mask.is_contiguous():
+        raise ValueError(f"{what}: mask must be a contiguous tensor on the GPU")
+    _obj_int(what, "n_classes", n_classes, 1, OBJ_MAX_CLASSES)
+    _obj_int(what, "background", background, 0, 255)
+    _obj_int(what, "radius", radius, 1, OBJ_MAX_RADIUS)
+    excl = _edt_exclude(what, exclude)
+    if excl == background:
+        raise ValueError(f"{what}: exclude and background are both {background}")
+    B, H, W = (int(v) for v in mask.shape)
+    need = object_edt_workspace(B, H, W)
+    if not isinstance(ws, torch.Tensor) or not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < need or ws.data_ptr() % 16:
+        raise ValueError(f"{what}: the workspace must be a contiguous, 16-byte aligned GPU tensor of at least {need} bytes")
+    for name, t, dt in (("d1", d1, torch.int32), ("d2", d2, torch.int32), ("pw", pw, torch.float32)):
+        if t is not None:
+            _pp_tensor(what, name, t, dt)
+            if t.numel() != mask.numel():
+                raise ValueError(f"{what}: {name} holds {t.numel()} elements, the masks {mask.numel()}")
+    if class_w is not None:
+        _pp_tensor(what, "class_w", class_w, torch.float32, numel=n_classes)
+    if any(t is not None and t.device != mask.device for t in (ws, d1, d2, pw, class_w)):
+        raise ValueError(f"{what}: every tensor must live on one device")
+    check(lib.unet_object_edt(mask.data_ptr(), int(mask.dtype == torch.int64), B, H, W, background, excl, n_classes, radius, ws.data_ptr(),
+                              _p(d1), _p(d2), _p(class_w), float(w0), float(sigma), _p(pw), _stream()), what)
+
+
+def object_edt(mask: torch.Tensor, d1: torch.Tensor, d2: torch.Tensor, ws: torch.Tensor, background: int = 0, exclude=None,
+               n_classes: int = OBJ_MAX_CLASSES, radius: int = 30):
+    """d1, d2 int32 [B, H, W] = for a background pixel the squared Euclidean distances to the nearest and the second nearest distinct
+    object of its image within `radius`, OBJ_NO_OBJECT where there is none and off the background; mask uint8 or int64 [B, H, W]; ws: a
+    16-byte aligned tensor of at least object_edt_workspace(B, H, W) bytes (unet_hip.h has the rules).  No host sync."""
+    if d1 is None or d2 is None:
+        raise ValueError("object_edt: d1 and d2 must be int32 tensors")
+    _object_call("object_edt", mask, ws, background, exclude, n_classes, radius, d1, d2, None, 0.0, 1.0, None)
+
+
+def object_border_weight(mask: torch.Tensor, class_w, n_classes: int, w0: float, sigma: float, pw: torch.Tensor, ws: torch.Tensor,
+                         background: int = 0, exclude=None, radius: int = 30):
+    """pw float32 [B, H, W] = class_w[y] + w0 * exp(-(sqrt D1 + sqrt D2)^2 / (2 sigma^2)) with D1, D2 of object_edt; class_w float32 [n_classes]
+    or None (ones); a value outside [0, n_classes) gives 0, D2 == OBJ_NO_OBJECT a second term of exactly 0.  The same launches as
+    object_edt: the row pass writes the map instead of the distances.  No host sync."""
+    if not w0 >= 0 or not sigma > 0:
+        raise ValueError(f"object_border_weight: needs w0 >= 0 and sigma > 0, got {w0!r} and {sigma!r}")
+    if pw is None:
+        raise ValueError("object_border_weight: pw must be a float32 tensor")
+    _object_call("object_border_weight", mask, ws, background, exclude, n_classes, radius, None, None, class_w, w0, sigma, pw)
