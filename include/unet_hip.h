@@ -937,6 +937,25 @@ int unet_zonal_lds_bins(void);
 int unet_zonal_counts(const int32_t* zones, const uint8_t* mask, const int32_t* labels, int H, int W, int Z, int C, long long* counts,
                       long long* objects, long long* bad, void* stream);
 
+/* ------------------------------------------------------ zonal statistics of a float plane --
+ * Count, sum, sum of squares, minimum and maximum of a float32 plane per zone (csrc/zonal_values.hip, unet_amd/zonal.py, DESIGN 3.25, where
+ * the rules are).  zones as above, values float32 [H, W]; 1 <= H, W < 2^20, H * W <= 2^31 - 1, 1 <= Z < 2^23.  A pixel is valid iff its zone
+ * lies in 0 .. Z - 1, its value is finite and, with has_nodata = 1, differs from nodata.
+ * zonal_absmax: *absmax (one 64-bit word, reset first) = the largest bit pattern of |v| over the valid pixels, 0 where there is none: a maximum per
+ *   wavefront, then one unsigned atomic maximum each.
+ * zonal_values: sums (uint64 [5, Z]: pixels, valid, sum_q, sq_lo, sq_hi; sum_q in two's complement) and minmax (float32 [2, Z]: min, max),
+ *   both initialised here.  pixels counts every pixel of a zone, the others its valid pixels: q = rint(double(v) * 2^shift), half to even,
+ *   -98 <= shift <= 178, and q^2 = hi * 2^30 + lo with 0 <= lo < 2^30, split before anything is summed, so that with |q| <= 2^30 every sum
+ *   stays within 2^61.  min and max are the exact float32 extremes (unsigned atomics on the order-preserving image of the bits, decoded in
+ *   place by a last launch); a zone without a valid pixel holds +inf and -inf.  *bad is reset and gains bit 1 for a zone outside
+ *   -1 .. Z - 1 (counted nowhere) and bit 2 for a valid pixel with |q| > 2^30 (left out of the sums).  Every accumulation is an integer
+ *   atomic add, minimum or maximum, so the result does not depend on the order of arrival.  16-byte accesses where zones and values are
+ *   16-byte aligned; no access outside the H * W elements.  Bad arguments return -1 before any launch. */
+int unet_zonal_absmax(const int32_t* zones, const float* values, int H, int W, int Z, int has_nodata, float nodata, long long* absmax,
+                      void* stream);
+int unet_zonal_values(const int32_t* zones, const float* values, int H, int W, int Z, int has_nodata, float nodata, int shift,
+                      long long* sums, float* minmax, long long* bad, void* stream);
+
 /* ------------------------------------------------------ object attributes --
  * A keyed reduction per object over a label image (csrc/objects.hip, unet_amd/objects.py, DESIGN 3.23, where the rules are).  mask is uint8
  * [H, W], labels int32 [H, W] (labels[p] = the smallest linear index of the object of pixel p; p is an anchor iff labels[p] == p), 1 <= H, W

@@ -110,6 +110,9 @@ INSTANCES_RASTER = False
 # number of objects (components, or the instances of INSTANCES) per zone and class; an object counts in the zone of its first pixel
 ZONES = None
 ZONAL_OBJECTS = False
+# ZONAL_VALUES False | True (needs ZONES, merge = True and a float output: regression or specific_class): the table holds pixels, area, valid,
+# mean, std, min, max and sum of the predicted float plane per zone -- mean predicted cover per parcel -- instead of the class counts
+ZONAL_VALUES = False
 # attributes of every object of the merged class mask (merge = True, class output), measured on the GPU (unet_amd/objects.py): OBJECTS False |
 # True writes <merged raster stem>_objects.geojson, one point per object (component, or instance of INSTANCES) inside it, with pixels, area,
 # perimeter, centroid, bbox, diameter, compactness and on_edge -- a tree list with crown diameters; with VECTOR the polygons carry the same
@@ -125,6 +128,7 @@ def main():
     global large_file, specific_class, all_classes, transforms, VALID_SCENES, self_attention, monitor, loss_func, LR_FINDER
     global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS
     global VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY, INSTANCES, INSTANCES_RASTER, ZONES, ZONAL_OBJECTS, OBJECTS, OBJECTS_EXCLUDE
+    global ZONAL_VALUES
     t0 = time.time()
     if enable_extra_parameters:          # params_and_main.py:129-145
         import warnings
@@ -137,7 +141,7 @@ def main():
         TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS = None, "mean", None, None, None, None
         VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY = False, None, None
         INSTANCES, INSTANCES_RASTER = None, False
-        ZONES, ZONAL_OBJECTS = None, False
+        ZONES, ZONAL_OBJECTS, ZONAL_VALUES = None, False, False
         OBJECTS, OBJECTS_EXCLUDE = False, None
     if Create_tiles:
         from create_tiles_unet import split_raster
@@ -167,6 +171,8 @@ def main():
             extra["instances"], extra["instances_raster"] = INSTANCES, INSTANCES_RASTER
         if ZONES is not None:
             extra["zones"], extra["zonal_objects"] = ZONES, ZONAL_OBJECTS
+        if ZONAL_VALUES:
+            extra["zonal_values"] = True
         if OBJECTS:
             extra["objects"], extra["objects_exclude"] = True, OBJECTS_EXCLUDE
         save_predictions(predict_model, predict_path, regression, merge, all_classes, specific_class, large_file, AOI, year,

@@ -34,7 +34,8 @@ The output options beyond the reference, each described at ``predict_raster``: `
 mask, ``unet_amd/postprocess.py``), ``compress=`` / ``predictor=`` / ``tile=`` / ``overviews=`` (LZW GeoTIFFs, tiled and with overviews),
 ``vector_path=`` / ``vector=True`` with ``vector_exclude=`` and ``vector_simplify=`` (the mask's polygons as GeoJSON, ``unet_amd/vectorize.py``) and
 ``instances=`` (touching objects split into instances, ``unet_amd/instances.py``) and ``zones_path=`` / ``zones=`` with ``zonal_objects=`` (pixels, shares
-and objects of every class per polygon zone, ``unet_amd/zonal.py``).  ``check_outputs``, the first statement of both entry points,
+and objects of every class per polygon zone, ``unet_amd/zonal.py``; with ``zonal_values=`` the mean, std, min, max and sum of a regression or
+``specific_class`` plane per zone instead).  ``check_outputs``, the first statement of both entry points,
 checks them from the arguments alone (ValueError before the model is loaded) into one ``OutputPlan``.  ``_write_outputs`` is the one output stage,
 on rank 0 and on the assembled mask, so N ranks equal 1 rank by construction: instances, the vector file, the zonal table, the raster.  The plan keeps the merged
 array where the merge assembled it while a stage needs it there: with one rank the mask goes from the argmax through the filters, the split and
@@ -65,7 +66,7 @@ from unet_amd.tiffio import check_compress, check_tiling, read_tiff, resolve_ove
 from unet_amd.tta import parse as tta_codes
 from unet_amd.vectorize import check_vector, epsg_of_tags, vectorize_mask
 from unet_amd.instances import Instances, check_instances
-from unet_amd.zonal import check_zones, zonal_mask
+from unet_amd.zonal import check_zones, zonal_mask, zonal_plane
 from unet_amd.objects import check_objects, objects_mask
 
 
@@ -116,6 +117,7 @@ class OutputPlan:
     instances: Optional[Instances] = None
     instances_raster: bool = False
     zones: bool = False                               # a zonal table is written
+    zonal_values: bool = False                        # ... of the float plane (zonal_plane) instead of the class mask (zonal_mask)
     zonal_objects: bool = False
     objects: Optional[tuple] = None                   # the classes that are not measured; None: no objects file
 
@@ -137,14 +139,32 @@ class OutputPlan:
         if not self.merge:
             raise ValueError(f"{subject} needs merge=True: per-tile outputs are not {done}")
 
+    def needs_plane(self, zones: bool, zonal_objects: bool):
+        """the rule of zonal_values: the statistics of the output's one float plane per zone"""
+        if not zones:
+            raise ValueError("zonal_values without zones")
+        if zonal_objects:
+            raise ValueError("zonal_values with zonal_objects: objects are counted on the class mask")
+        if self.mask:
+            raise ValueError("zonal_values needs a float plane, regression or specific_class: the class mask has none (its table is zones "
+                             "without zonal_values)")
+        if self.all_classes:
+            raise ValueError("zonal_values needs one float plane: not with all_classes")
+        if self.large_file:
+            raise ValueError("zonal_values needs the float plane on one device: not with large_file")
+        if not self.merge:
+            raise ValueError("zonal_values needs merge=True: per-tile outputs are not summarised")
+
 
 def check_outputs(regression=False, all_classes=False, specific_class=None, large_file=False, merge=True, class_zero=False, blend="mean",
                   postprocess=None, compress=None, predictor=1, tile=None, overviews=None, vector=None, vector_exclude=None, vector_simplify=None,
-                  instances=None, instances_raster=False, raster=True, return_array=True, raster_arg="instances_raster", objects=None,
-                  objects_exclude=None, zones=None, zonal_objects=False) -> OutputPlan:
+                  instances=None, instances_raster=False, raster=True, return_array=True, raster_arg="instances_raster", *, zonal_values=False,
+                  objects=None, objects_exclude=None, zones=None, zonal_objects=False) -> OutputPlan:
     """Every check of the two entry points' output arguments, from the arguments alone and in one order -> the OutputPlan.  vector: vector= or
     vector_path=; instances_raster: whether the argument named raster_arg asks for the instance raster; raster: whether out_path is given;
-    objects: objects= or objects_path=; zones: zones= or zones_path= (the entry points check that its output path is there)"""
+    objects: objects= or objects_path=; zones: zones= or zones_path= (the entry points check that its output path is there); zonal_values:
+    the table summarises the one float plane of the output (regression, specific_class) instead of the class mask.  Everything from
+    zonal_values on is passed by keyword, as both entry points always did, so that a new argument can never shift a positional one"""
     mode = OutputPlan(bool(regression), bool(all_classes), specific_class, bool(large_file), bool(merge), bool(class_zero), bool(raster))
     check_blend(blend, large_file, merge)
     post = check_postprocess(postprocess)
@@ -167,13 +187,15 @@ def check_outputs(regression=False, all_classes=False, specific_class=None, larg
         if vec is None and not instances_raster and zones is None and obj is None:
             raise ValueError("instances without an output: ask for the vector file, the instance raster or both")
     zonal = check_zones(zones, zonal_objects)
-    if zonal:
+    if zonal_values:
+        mode.needs_plane(zonal, zonal_objects)
+    elif zonal:
         mode.needs_mask("zonal statistics", "summarised")
     if not return_array and not raster and vec is None and not zonal and obj is None:
         raise ValueError("return_array=False needs out_path: the prediction would go nowhere")
     return dataclasses.replace(mode, blend=blend, postprocess=post, compress=compress, predictor=predictor, tile=tile, overviews=overviews,
                                vector=vec, vector_simplify=vector_simplify, instances=inst, instances_raster=bool(instances_raster),
-                               zones=zonal, zonal_objects=bool(zonal_objects), objects=obj)
+                               zones=zonal, zonal_values=bool(zonal_values), zonal_objects=bool(zonal_objects), objects=obj)
 
 
 def _write_outputs(plan: OutputPlan, out, device, gt, tags, raster_path, vector_path, instances_path, class_names, timing, zones_path=None,
@@ -205,7 +227,10 @@ def _write_outputs(plan: OutputPlan, out, device, gt, tags, raster_path, vector_
     if plan.zones:
         out = torch.as_tensor(out)
         out = (out if out.is_cuda else out.to(device)).contiguous()
-        zonal_mask(out, zones_path, zonal_path, gt, tags, class_names, plan.class_zero, labels, plan.zonal_objects, timing)
+        if plan.zonal_values:
+            zonal_plane(out, zones_path, zonal_path, gt, tags, plan.nodata, timing)
+        else:
+            zonal_mask(out, zones_path, zonal_path, gt, tags, class_names, plan.class_zero, labels, plan.zonal_objects, timing)
     if not plan.encode_in_place and isinstance(out, torch.Tensor):
         out = out.cpu().numpy()
     if raster_path is not None:
@@ -483,7 +508,7 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                    batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
                    return_array: bool = True, tile=None, overviews=None, vector_path=None, vector_exclude=None, vector_simplify=None,
                    instances=None, instances_path=None, zones_path=None, zonal_path=None, zonal_objects: bool = False,
-                   objects_path=None, objects_exclude=None):
+                   objects_path=None, objects_exclude=None, zonal_values: bool = False):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -549,6 +574,10 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
              for the class mask and not with large_file (ValueError).  Under class_zero the NO_Data class 0 is not measured.  timing gains
              objects_seconds and objects
     objects_exclude  None | int | iterable of class ids (the model's, before the class_zero shift) whose objects are not measured
+    zonal_values  True (needs zones_path): the table summarises the one float plane of the output instead of the class mask -- regression
+             (nodata -9999 is not a valid pixel) or specific_class -- as pixels, area, valid, mean, std, min, max and sum per zone, summed
+             on the device in fixed point so that the table does not depend on scheduling (unet_amd/zonal.py); not for the class mask,
+             all_classes, large_file or with zonal_objects (ValueError)
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
@@ -557,7 +586,8 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
     plan = check_outputs(regression, all_classes, specific_class, large_file, True, class_zero, blend, postprocess, compress, predictor, tile,
                          overviews, vector_path, vector_exclude, vector_simplify, instances, instances_raster=instances_path is not None,
                          raster=out_path is not None, return_array=return_array, raster_arg="instances_path", objects=objects_path,
-                         objects_exclude=objects_exclude, zones=zones_path, zonal_objects=zonal_objects)
+                         objects_exclude=objects_exclude, zones=zones_path, zonal_objects=zonal_objects,
+                         zonal_values=zonal_values)
     model = getattr(model, "model", model)
     codes = tta_codes(tta, [(size, size)])
     rank, _, world = _dist_ctx()
@@ -761,7 +791,8 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
                      AOI=None, year=None, validation_vision=True, class_zero=False, batch_size=16, timing: Optional[dict] = None,
                      batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
                      tile=None, overviews=None, vector: bool = False, vector_exclude=None, vector_simplify=None, instances=None,
-                     instances_raster: bool = False, zones=None, zonal_objects: bool = False, objects: bool = False, objects_exclude=None):
+                     instances_raster: bool = False, zones=None, zonal_objects: bool = False, objects: bool = False, objects_exclude=None,
+                     zonal_values: bool = False):
     """tta, blend, postprocess, compress / predictor, tile / overviews, vector_exclude, vector_simplify and instances are predict_raster's (see
     there); the ValueErrors of check_outputs come before the model is loaded.  What differs here: tta applies to merged and per-tile outputs
     alike; blend, postprocess, vector and instances need merge=True (per-tile outputs: no overlap to blend, not post-processed, polygonized, split).
@@ -773,10 +804,12 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     zones file; the table is written as <merged raster stem>_zonal.geojson beside the merged raster, with the class names of the vocab.
     objects (predict_raster's objects_path, with objects_exclude): True writes <merged raster stem>_objects.geojson beside the merged raster,
     one Point feature per object with its attributes and the class names of the vocab; it counts as an output of instances.
+    zonal_values (predict_raster's, needs zones and merge=True): <merged raster stem>_zonal.geojson holds the statistics of the float plane.
     validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
     plan = check_outputs(regression, all_classes, specific_class, large_file, merge, class_zero, blend, postprocess, compress, predictor, tile,
                          overviews, vector or None, vector_exclude, vector_simplify, instances, instances_raster, objects=objects or None,
-                         objects_exclude=objects_exclude, zones=zones, zonal_objects=zonal_objects)
+                         objects_exclude=objects_exclude, zones=zones, zonal_objects=zonal_objects,
+                         zonal_values=zonal_values)
     rank, local_rank, world = _dist_ctx()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model

@@ -299,6 +299,8 @@ _sig = {
     "unet_ras_resolve_ids": (i, [vp, i, i, vp, vp]),
     "unet_zonal_lds_bins": (i, []),
     "unet_zonal_counts": (i, [vp, vp, vp, i, i, i, i, vp, vp, vp, vp]),
+    "unet_zonal_absmax": (i, [vp, vp, i, i, i, i, C.c_float, vp, vp]),
+    "unet_zonal_values": (i, [vp, vp, i, i, i, i, C.c_float, i, vp, vp, vp, vp]),
     "unet_obj_point_packed": (i, [i, i]),
     "unet_obj_compact": (i, [vp, vp, vp, ll, ll, vp, vp, vp]),
     "unet_obj_accumulate": (i, [vp, vp, vp, i, i, C.POINTER(C.c_uint32), ll, vp, vp, vp, vp]),

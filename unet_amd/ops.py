@@ -2047,6 +2047,68 @@ def zonal_counts(zones: torch.Tensor, mask: torch.Tensor, labels: Optional[torch
                                 _stream()), what)
 
 
+# ---------------------------------------------------------------------------------------------- zonal statistics of float planes (csrc/zonal_values.hip)
+
+ZONAL_MIN_SHIFT, ZONAL_MAX_SHIFT = -98, 178         # 30 - E over the frexp exponents E of float32
+
+
+def check_zonal_values_sizes(what: str, shape, Z) -> tuple:
+    """(H, W, Z) with H, W within check_raster_shape, H * W <= 2^31 - 1 (the bound of the sums) and 1 <= Z < 2^23"""
+    H, W = check_raster_shape(what, shape)
+    if H * W > VEC_MAX_COUNT:
+        raise ValueError(f"{what}: the sums are bounded for at most 2^31 - 1 pixels, got {H} x {W}")
+    if isinstance(Z, bool) or not isinstance(Z, int):
+        raise ValueError(f"{what}: the number of zones must be an int, got {Z!r}")
+    if not 1 <= Z < RAS_MAX_FEATURES:
+        raise ValueError(f"{what}: the number of zones must lie in 1..2^23 - 1, got {Z}")
+    return H, W, Z
+
+
+def check_zonal_nodata(what: str, nodata) -> tuple:
+    """(has_nodata, nodata as the float32 the kernels compare with) of None or a real number"""
+    if nodata is None:
+        return 0, 0.0
+    if isinstance(nodata, bool) or not isinstance(nodata, (int, float)) or nodata != nodata:
+        raise ValueError(f"{what}: nodata must be None or a number, got {nodata!r}")
+    return 1, float(nodata)
+
+
+def check_zonal_shift(what: str, shift) -> int:
+    if isinstance(shift, bool) or not isinstance(shift, int) or not ZONAL_MIN_SHIFT <= shift <= ZONAL_MAX_SHIFT:
+        raise ValueError(f"{what}: shift must be an int in -98..178, got {shift!r}")
+    return shift
+
+
+def zonal_absmax(zones: torch.Tensor, values: torch.Tensor, Z: int, nodata, absmax: torch.Tensor):
+    """absmax (int64[1], reset) = the largest bit pattern of |values| over the valid pixels: zone in 0 .. Z - 1, value finite and not nodata"""
+    what = "zonal_absmax"
+    H, W, Z = check_zonal_values_sizes(what, zones.shape if isinstance(zones, torch.Tensor) else (), Z)
+    has, nd = check_zonal_nodata(what, nodata)
+    _table_tensor(what, "zones", zones, torch.int32, (H, W))
+    _table_tensor(what, "values", values, torch.float32, (H, W))
+    _table_tensor(what, "absmax", absmax, torch.int64, (1,))
+    _on_one_device(what, [("zones", zones), ("values", values), ("absmax", absmax)])
+    check(lib.unet_zonal_absmax(zones.data_ptr(), values.data_ptr(), H, W, Z, has, nd, absmax.data_ptr(), _stream()), what)
+
+
+def zonal_values(zones: torch.Tensor, values: torch.Tensor, Z: int, nodata, shift: int, sums: torch.Tensor, minmax: torch.Tensor, bad: torch.Tensor):
+    """sums (int64 [5, Z]: pixels, valid, sum_q, sq_lo, sq_hi) and minmax (float32 [2, Z]) of the zones under q = rint(double(v) * 2^shift),
+    both initialised by the call; bad (int64[1]) is reset and gains bit 1 for a zone outside -1 .. Z - 1 and bit 2 for a valid pixel with
+    |q| > 2^30 (unet_hip.h)"""
+    what = "zonal_values"
+    H, W, Z = check_zonal_values_sizes(what, zones.shape if isinstance(zones, torch.Tensor) else (), Z)
+    has, nd = check_zonal_nodata(what, nodata)
+    check_zonal_shift(what, shift)
+    _table_tensor(what, "zones", zones, torch.int32, (H, W))
+    _table_tensor(what, "values", values, torch.float32, (H, W))
+    _table_tensor(what, "sums", sums, torch.int64, (5, Z))
+    _table_tensor(what, "minmax", minmax, torch.float32, (2, Z))
+    _table_tensor(what, "bad", bad, torch.int64, (1,))
+    _on_one_device(what, [("zones", zones), ("values", values), ("sums", sums), ("minmax", minmax), ("bad", bad)])
+    check(lib.unet_zonal_values(zones.data_ptr(), values.data_ptr(), H, W, Z, has, nd, shift, sums.data_ptr(), minmax.data_ptr(), bad.data_ptr(),
+                                _stream()), what)
+
+
 # ---------------------------------------------------------------------------------------------- object attributes (csrc/objects.hip)
 
 def check_objects_shape(what: str, shape) -> tuple:

@@ -25,13 +25,40 @@ and from step to step -- a wavefront whose 256 pixels hold one key carries (key,
 plane and writes it when the key changes.  Memory: 4 bytes per pixel for the zone plane next to the rasterizer's own buffers (unet_amd/rasterize.py),
 16 Z C bytes for the two tables.  Every buffer that a kernel writes comes from _alloc.
 
-write_zonal and read_zones are host code on the json and csv modules.  Out of scope: statistics of float planes, overlapping zones counted
-more than once, ALL_TOUCHED, line and point zones, reprojection, Shapefile and GeoPackage, per-tile outputs, tables accumulated across ranks
-(the stage runs on rank 0's assembled mask, as the vector stage does), and a host fallback (without a device the device calls raise)."""
+Float planes (zonal_values, csrc/zonal_values.hip): count, mean, standard deviation, minimum, maximum and sum of a float32 plane
+-- a regression output, the probability of one class -- per zone.  tests/zonal_values_ref.py restates these rules; the device tables equal
+it bit for bit.
+Inputs      the zone plane as above, a value plane float32 [H, W], an optional nodata (a number, or None).  H * W <= 2^31 - 1 and Z < 2^23
+            (ValueError before any launch).
+Valid       a pixel is valid iff its zone is >= 0, its value is finite and its value does not equal nodata.  pixels[z] counts all pixels of
+            zone z, valid[z] the valid ones: NaN, +-inf and nodata pixels count in pixels only.
+Fixed point floating adds depend on their order, integer adds do not: A = the largest |v| over the valid pixels, E = 0 when A = 0, else the
+            frexp exponent, 2^(E-1) <= A < 2^E; the shift is s = 30 - E (-98 .. 178), and every valid value becomes q = rint(double(v) * 2^s),
+            half to even, |q| <= 2^30.  float32 -> double and the scaling by a power of two are exact, so
+            np.rint(np.ldexp(v.astype(np.float64), s)).astype(np.int64) gives the same integers.  shift= fixes s instead, so that the tables
+            of several rasters, tiles or ranks add up; a valid pixel with |q| > 2^30 then sets a word that the host reads once after the
+            launch: ValueError.
+Tables      pixels, valid, sum_q = sum q, sq_lo = sum lo and sq_hi = sum hi with q^2 = hi * 2^30 + lo, 0 <= lo < 2^30: int64 [Z].  Each term is
+            at most 2^30 and a plane holds fewer than 2^31 pixels, so every sum stays within 2^61 and nothing wraps.  min and max
+            (float32 [Z]) are the exact extremes of the valid pixels, by unsigned atomic minimum and maximum on the order-preserving image
+            of the float bits (-0.0 lies below +0.0); a zone without a valid pixel holds +inf and -inf on the device.
+Derived     on the host, in Python integers and one division (zonal_value_rows): mean = sum_q / valid * 2^-s, population std =
+            sqrt(SQ * valid - sum_q^2) / valid * 2^-s with SQ = sq_hi * 2^30 + sq_lo, sum = sum_q * 2^-s; a zone with valid == 0 has None
+            for mean, std, min, max and sum.
+Accuracy    |q * 2^-s - v| <= 2^(E-31) for every valid pixel, so the mean differs from the float64 mean of the raw floats by at most
+            2^(E-31) plus float64 rounding: 2^-31 of the plane's largest magnitude, 128 times finer than a float32 ulp at that magnitude.
+Bad input   a zone outside -1 .. Z - 1 is counted nowhere, indexes nothing and raises ValueError after the launch, as in zonal_counts.
+
+write_zonal and read_zones are host code on the json and csv modules.  Out of scope: several float planes at once (all_classes), median,
+percentiles and histograms, weighted or fractional pixel coverage, float64 and integer value planes, per-object float statistics (pass dense
+object ids as the zone plane), overlapping zones counted more than once, ALL_TOUCHED, line and point zones, reprojection, Shapefile and
+GeoPackage, per-tile outputs, tables accumulated across ranks (the stage runs on rank 0's assembled output, as the vector stage does), and a
+host fallback (without a device the device calls raise)."""
 from __future__ import annotations
 
 import csv
 import json
+import math
 import os
 import re
 import time
@@ -77,12 +104,12 @@ def rasterize_ids(rings_or_polygons, shape, stages: Optional[dict] = None) -> to
     return ids
 
 
-def _plane(a, dtype, name: str, device=None) -> torch.Tensor:
+def _plane(a, dtype, name: str, device=None, what: str = "zonal_counts") -> torch.Tensor:
     """a contiguous [H, W] device tensor of `dtype` from a device tensor, a host tensor or a NumPy array (host input is uploaded)"""
     if isinstance(a, np.ndarray):
         a = torch.from_numpy(np.ascontiguousarray(a))
     if not isinstance(a, torch.Tensor) or a.dtype != dtype or a.dim() != 2:
-        raise ValueError(f"zonal_counts: {name} must be a {dtype} [H, W] tensor or array, got {getattr(a, 'dtype', type(a).__name__)} "
+        raise ValueError(f"{what}: {name} must be a {dtype} [H, W] tensor or array, got {getattr(a, 'dtype', type(a).__name__)} "
                          f"{tuple(getattr(a, 'shape', ()))}")
     if not a.is_cuda:
         a = a.to(device if device is not None else "cuda")
@@ -118,6 +145,117 @@ def zonal_counts(zones, mask, n_zones: int, n_classes: int, labels=None, stages:
     if word:
         raise ValueError(f"zonal_counts: the zone plane holds a value outside -1..{Z - 1}")
     return ZonalStats(counts, objects)
+
+
+# ------------------------------------------------------------------------------------------------------------------ float planes
+
+Q_BITS = 30          # |q| <= 2^30
+
+
+@dataclass
+class ZonalValues:
+    """the tables of zonal_values: pixels, valid, sum_q, sq_lo, sq_hi int64 [Z], min and max float32 [Z] (+inf / -inf for a zone without a
+    valid pixel), and the shift s of q = rint(v * 2^s).  Tables of one shift add up (min and max combine by minimum and maximum).  table:
+    the one int64 [6, Z] allocation that the seven are views of (row 5 holds min and max), so that one copy moves them all"""
+    pixels: torch.Tensor
+    valid: torch.Tensor
+    sum_q: torch.Tensor
+    sq_lo: torch.Tensor
+    sq_hi: torch.Tensor
+    min: torch.Tensor
+    max: torch.Tensor
+    shift: int
+    table: Optional[torch.Tensor] = None
+
+    @staticmethod
+    def of_table(table: torch.Tensor, shift: int) -> "ZonalValues":
+        Z = table.shape[1]
+        mm = table[5].view(torch.float32).view(2, Z)
+        return ZonalValues(table[0], table[1], table[2], table[3], table[4], mm[0], mm[1], shift, table)
+
+    def cpu(self) -> "ZonalValues":
+        if self.table is not None:
+            return ZonalValues.of_table(self.table.cpu(), self.shift)          # the one copy
+        return ZonalValues(*(t.cpu() for t in (self.pixels, self.valid, self.sum_q, self.sq_lo, self.sq_hi, self.min, self.max)), self.shift)
+
+
+_NUMPY_DTYPE = {torch.int32: np.dtype(np.int32), torch.float32: np.dtype(np.float32)}
+
+
+def _has_dtype(a, dtype) -> bool:
+    """whether a tensor or a NumPy array holds elements of the torch `dtype`"""
+    return a.dtype == dtype if isinstance(a, torch.Tensor) else isinstance(a, np.ndarray) and a.dtype == _NUMPY_DTYPE[dtype]
+
+
+def shift_of_absmax(bits: int) -> int:
+    """the shift 30 - E of the largest |v|, given as its float32 bit pattern: E = 0 for 0, else the frexp exponent, 2^(E-1) <= A < 2^E"""
+    a = float(np.array([bits], dtype=np.uint32).view(np.float32)[0])
+    if not np.isfinite(a):
+        raise ValueError(f"zonal_values: the largest |value| is not finite (bits {bits:#x})")
+    return Q_BITS - (math.frexp(a)[1] if a else 0)
+
+
+def zonal_values(zones, values, n_zones: int, nodata=None, shift: Optional[int] = None, stages: Optional[dict] = None) -> ZonalValues:
+    """ZonalValues (device tensors) of a zone plane (int32 [H, W], -1 = no zone) and a value plane (float32 [H, W]) under the rules of the
+    module docstring.  nodata: a number whose pixels are not valid, or None.  shift: None derives it from the largest |value| of the valid
+    pixels (one more pass and one host read); an int fixes it, so that the tables of several rasters or tiles add up -- a valid pixel with
+    |q| > 2^30 is then a ValueError.  Host inputs are uploaded.  ValueError for a zone outside -1 .. n_zones - 1 (read from the device after
+    the launch) and for every limit (before it).  stages: a dict that receives the milliseconds of `absmax` and `values` (this synchronises
+    the device: for measurements only)."""
+    what = "zonal_values"
+    H, W, Z = ops.check_zonal_values_sizes(what, tuple(getattr(zones, "shape", ())), n_zones)
+    if tuple(getattr(values, "shape", ())) != (H, W):
+        raise ValueError(f"{what}: values has shape {tuple(getattr(values, 'shape', ()))}, the zones {(H, W)}")
+    ops.check_zonal_nodata(what, nodata)
+    if shift is not None:
+        ops.check_zonal_shift(what, shift)
+    for name, t, dtype in (("zones", zones, torch.int32), ("values", values, torch.float32)):          # before the device is asked for
+        if not _has_dtype(t, dtype):
+            raise ValueError(f"{what}: {name} must be a {dtype} [H, W] tensor or array, got {getattr(t, 'dtype', type(t).__name__)}")
+    if not torch.cuda.is_available():
+        raise ValueError("zonal_values runs on the GPU and there is no device (it has no host fallback)")
+    dev = next((t.device for t in (zones, values) if isinstance(t, torch.Tensor) and t.is_cuda), None)
+    z, v = _plane(zones, torch.int32, "zones", dev, what), _plane(values, torch.float32, "values", dev, what)
+    dev = z.device
+    st = _Stages(stages)
+    words = _alloc((2,), torch.int64, dev)          # the largest |v|, the bad word
+    if shift is None:
+        ops.zonal_absmax(z, v, Z, nodata, words[0:1])
+        shift = shift_of_absmax(ops.vec_read(words, 0, 1)[0])          # a host read
+        st.mark("absmax")
+    table = _alloc((6, Z), torch.int64, dev)
+    out = ZonalValues.of_table(table, shift)
+    ops.zonal_values(z, v, Z, nodata, shift, table[:5], table[5].view(torch.float32).view(2, Z), words[1:2])
+    word = ops.vec_read(words, 1, 1)[0]          # the host read
+    st.mark("values")
+    if word & 2:
+        raise ValueError(f"{what}: the zone plane holds a value outside -1..{Z - 1}")
+    if word:
+        raise ValueError(f"{what}: a value times 2^{shift} exceeds 2^{Q_BITS}: shift={shift} is too large for this plane")
+    return out
+
+
+def zonal_value_rows(stats: ZonalValues, pixel_area: float = 1.0) -> list:
+    """the added properties of every zone, one ordered dict each: pixels (all pixels of the zone inside the raster), area (pixels x
+    pixel_area), valid (the pixels with a finite value other than nodata) and mean, std (population), min, max, sum of those.  The sums are
+    Python integers up to one division: mean = sum_q / valid * 2^-s, std = sqrt(SQ * valid - sum_q^2) / valid * 2^-s with SQ = sq_hi * 2^30
+    + sq_lo.  A zone without a valid pixel has None for all five."""
+    host = [(t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for t in
+            (stats.pixels, stats.valid, stats.sum_q, stats.sq_lo, stats.sq_hi, stats.min, stats.max)]
+    if any(a.ndim != 1 or a.shape != host[0].shape for a in host):
+        raise ValueError(f"the tables must be [Z] each, got {[a.shape for a in host]}")
+    s = int(stats.shift)
+    rows = []
+    for pixels, valid, sum_q, lo, hi, mn, mx in zip(*(a.tolist() for a in host)):
+        row = {"pixels": pixels, "area": pixels * float(pixel_area), "valid": valid}
+        if valid:
+            sq = (hi << Q_BITS) + lo
+            row.update(mean=math.ldexp(sum_q / valid, -s), std=math.ldexp(math.sqrt(sq * valid - sum_q * sum_q) / valid, -s), min=mn, max=mx,
+                       sum=math.ldexp(float(sum_q), -s))
+        else:
+            row.update(mean=None, std=None, min=None, max=None, sum=None)
+        rows.append(row)
+    return rows
 
 
 # ------------------------------------------------------------------------------------------------------------------ files (host)
@@ -190,16 +328,25 @@ def zonal_rows(stats, codes=None, pixel_area: float = 1.0, class_zero: bool = Fa
     return rows
 
 
-def write_zonal(path, features, stats, codes=None, pixel_area: float = 1.0, class_zero: bool = False, crs=None) -> int:
+def write_zonal(path, features, stats, codes=None, pixel_area: float = 1.0, class_zero: bool = False, crs=None, values=None) -> int:
     """The table of zonal_rows as a file; the suffix decides: .geojson -- one FeatureCollection of the zone features with their geometry
     and their own properties, the added ones behind them (an added name replaces an own property of that name); .csv -- one row per zone,
     the zones' own properties first (the union of their names in order of appearance, empty where a zone lacks one), None as an empty
     field.  features: read_zones' list, one entry per row of the tables.  crs: the "crs" member to write (None: the one read_zones kept).
-    Returns the number of zones.  Host code."""
+    values: a ZonalValues whose zonal_value_rows are written behind the class rows (pixels and area are common to both), or alone where
+    stats is None.  Returns the number of zones.  Host code."""
     suffix = os.path.splitext(os.fspath(path))[1].lower()
     if suffix not in (".geojson", ".csv"):
         raise ValueError(f"{path}: the zonal table is written as .geojson or .csv")
-    rows = zonal_rows(stats, codes, pixel_area, class_zero)
+    if values is None:
+        rows = zonal_rows(stats, codes, pixel_area, class_zero)
+    else:
+        rows = zonal_value_rows(values, pixel_area)
+        if stats is not None:
+            own = zonal_rows(stats, codes, pixel_area, class_zero)
+            if len(own) != len(rows) or any(a["pixels"] != b["pixels"] for a, b in zip(own, rows)):
+                raise ValueError("the class tables and the value tables are not of the same zones")
+            rows = [{**a, **b} for a, b in zip(own, rows)]
     if len(rows) != len(features):
         raise ValueError(f"the tables hold {len(rows)} zones, the features {len(features)}")
     crs = getattr(features, "crs", None) if crs is None else crs
@@ -266,4 +413,29 @@ def zonal_mask(mask, zones_path, out_path, geotransform=None, tags=None, codes=N
     write_zonal(out_path, feats, host, codes, 1.0 if gt is None else abs(gt[1] * gt[5]), class_zero)
     if timing is not None:
         timing.update(zonal_seconds=time.perf_counter() - t0, zonal_zones=len(feats), zonal_pixels=int(host.counts.sum()))
+    return host
+
+
+def zonal_plane(out, zones_path, out_path, geotransform=None, tags=None, nodata=None, timing: Optional[dict] = None) -> ZonalValues:
+    """The output stage of an assembled float plane (regression, or the probability of one class; device or host), the twin of zonal_mask:
+    read_zones on the raster's grid, the EPSG check, rasterize_ids, zonal_values with a derived shift, one copy of the tables to the host,
+    write_zonal (pixels, area, valid, mean, std, min, max, sum per zone).  nodata: the value of the plane's pixels without a prediction
+    (-9999 under regression), or None.  timing gains zonal_seconds, zonal_zones and zonal_pixels (the pixels in any zone).  Returns the
+    host tables."""
+    t0 = time.perf_counter()
+    if not torch.cuda.is_available():
+        raise ValueError("zonal statistics run on the GPU and there is no device (they have no host fallback)")
+    rings, feats = read_zones(zones_path, geotransform)
+    theirs, ours = epsg_of_crs(feats.crs), epsg_of_tags(tags)
+    if theirs is not None and ours is not None and theirs != ours:
+        raise ValueError(f"{zones_path}: the zones are in EPSG:{theirs}, the raster in EPSG:{ours} (there is no reprojection)")
+    if not len(feats):
+        raise ValueError(f"{zones_path}: no Polygon or MultiPolygon zone")
+    v = _plane(out, torch.float32, "values", None, "zonal_values")
+    ids = rasterize_ids(rings.to(v.device), v.shape)
+    host = zonal_values(ids, v, len(feats), nodata).cpu()          # the one copy
+    gt = None if geotransform is None else tuple(float(x) for x in geotransform)
+    write_zonal(out_path, feats, None, pixel_area=1.0 if gt is None else abs(gt[1] * gt[5]), values=host)
+    if timing is not None:
+        timing.update(zonal_seconds=time.perf_counter() - t0, zonal_zones=len(feats), zonal_pixels=int(host.pixels.sum()))
     return host
