@@ -120,16 +120,20 @@ def _codecs():
     global _codec_lib
     if _codec_lib is None:
         import ctypes as C
-        host = Path(__file__).resolve().parent / "lib" / "libunet_tiff.so"
+        from ._abi import signatures
+        here = Path(__file__).resolve().parent
+        host, include = here / "lib" / "libunet_tiff.so", here.parent / "include"
         if host.exists():
             lib = C.CDLL(str(host))
         else:
             from ._lib import lib
-        for fn in (lib.unet_tiff_lzw_decode, lib.unet_tiff_packbits_decode, lib.unet_tiff_lzw_encode):
-            fn.restype, fn.argtypes = C.c_longlong, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong]
+        sig = signatures(include / "unet_hip.h", {}, only=("unet_tiff_lzw_decode", "unet_tiff_packbits_decode", "unet_tiff_lzw_encode"))
+        for name, (res, args) in sig.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
         try:                       # include/unet_tiff.h: the JPEG decoder lives in the host-only library alone
-            lib.unet_tiff_jpeg_decode.restype = C.c_longlong
-            lib.unet_tiff_jpeg_decode.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
+            fn = lib.unet_tiff_jpeg_decode
+            fn.restype, fn.argtypes = signatures(include / "unet_tiff.h", {})["unet_tiff_jpeg_decode"]
             lib.has_jpeg = True
         except AttributeError:     # libunet_hip.so, or a libunet_tiff.so built before the decoder existed
             lib.has_jpeg = False
