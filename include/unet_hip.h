@@ -981,6 +981,26 @@ int unet_obj_accumulate(const uint8_t* mask, const int32_t* labels, const int32_
 int unet_obj_point(const uint8_t* mask, const int32_t* labels, const int32_t* offs, int H, int W, const uint32_t* exclude8, long long P,
                    const long long* sums, const long long* bad, long long* key64, int32_t* point, void* stream);
 
+/* ------------------------------------------- float statistics per object --
+ * Count, sum, sum of squares, minimum and maximum of a float32 plane per object, with the pixel of each extreme (csrc/object_values.hip,
+ * unet_amd/objects.py, DESIGN 3.26, where the rules are).  mask, labels, offs, exclude8 and P are those of obj_accumulate; values is float32
+ * [H, W].  A pixel is valid iff its class is not excluded, its value is finite and, with has_nodata, differs from nodata.
+ * obj_absmax: *absmax (one 64-bit word, reset first) = the largest bit pattern of |v| over the valid pixels, 0 where there is none.  It reads the
+ *   mask and the values only.
+ * obj_values: table (uint64 [6, P], initialised here): rows 0 .. 3 are valid, sum_q (two's complement), sq_lo and sq_hi of every object under
+ *   q = rint(double(v) * 2^shift), half to even, -98 <= shift <= 178, q^2 = hi * 2^30 + lo; rows 4 and 5 are min and max: while the pass runs
+ *   key(v) << 32 | p under an unsigned atomic minimum and key(v) << 32 | (0xFFFFFFFF - p) under an unsigned atomic maximum (key: the
+ *   order-preserving image of the float bits, p the linear index), so each extreme comes with the smallest index that attains it; a last
+ *   launch decodes them in place to the float32 bits in the low half of the word and the int32 index in the high half (+inf, -inf and -1
+ *   for an object without a valid pixel).  *bad is reset and gains the three bits of obj_accumulate (such runs are dropped) and bit 3 for a
+ *   valid pixel with |q| > 2^30 (left out of every table).  P = 0 (table may be null): the check alone.
+ * Every accumulation is an integer atomic add, minimum or maximum.  16-byte accesses where labels and values are 16-byte and mask 4-byte
+ * aligned; no access outside the H * W elements, no store outside the table.  Bad arguments return -1 before any launch. */
+int unet_obj_absmax(const uint8_t* mask, const float* values, int H, int W, const uint32_t* exclude8, int has_nodata, float nodata,
+                    long long* absmax, void* stream);
+int unet_obj_values(const uint8_t* mask, const int32_t* labels, const float* values, const int32_t* offs, int H, int W, const uint32_t* exclude8,
+                    long long P, int has_nodata, float nodata, int shift, long long* table, long long* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

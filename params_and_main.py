@@ -119,6 +119,12 @@ ZONAL_VALUES = False
 # attributes.  OBJECTS_EXCLUDE None | class id | list of class ids whose objects are not measured
 OBJECTS = False
 OBJECTS_EXCLUDE = None
+# a value per object (needs OBJECTS): OBJECTS_VALUES None | the path of a one-band GeoTIFF on the merged raster's grid (a canopy height model,
+# an NDVI): every object gains <OBJECTS_VALUES_NAME>_valid, _mean, _std, _sum, _min, _max and _peak_x, _peak_y, the place where the value peaks
+# (tree height and treetop).  OBJECTS_CONFIDENCE False | True: the same of the merged probability of the predicted class, as confidence_*
+OBJECTS_VALUES = None
+OBJECTS_VALUES_NAME = "value"
+OBJECTS_CONFIDENCE = False
 # a mask_path that ends in .geojson / .json holds polygons instead of a raster: Create_tiles burns them on the GPU onto the image's grid
 # (unet_amd/rasterize.py) with this integer property as the class id
 MASK_ATTRIBUTE = "class"
@@ -128,7 +134,7 @@ def main():
     global large_file, specific_class, all_classes, transforms, VALID_SCENES, self_attention, monitor, loss_func, LR_FINDER
     global ENCODER_FACTOR, ARCHITECTURE, enable_regression, max_empty, TTA, BLEND, POSTPROCESS, COMPRESS, TILE, OVERVIEWS
     global VECTOR, VECTOR_EXCLUDE, VECTOR_SIMPLIFY, INSTANCES, INSTANCES_RASTER, ZONES, ZONAL_OBJECTS, OBJECTS, OBJECTS_EXCLUDE
-    global ZONAL_VALUES
+    global ZONAL_VALUES, OBJECTS_VALUES, OBJECTS_VALUES_NAME, OBJECTS_CONFIDENCE
     t0 = time.time()
     if enable_extra_parameters:          # params_and_main.py:129-145
         import warnings
@@ -143,6 +149,7 @@ def main():
         INSTANCES, INSTANCES_RASTER = None, False
         ZONES, ZONAL_OBJECTS, ZONAL_VALUES = None, False, False
         OBJECTS, OBJECTS_EXCLUDE = False, None
+        OBJECTS_VALUES, OBJECTS_VALUES_NAME, OBJECTS_CONFIDENCE = None, "value", False
     if Create_tiles:
         from create_tiles_unet import split_raster
         split_raster(path_to_raster=image_path, path_to_mask=mask_path, base_dir=base_dir, patch_size=patch_size,
@@ -175,6 +182,10 @@ def main():
             extra["zonal_values"] = True
         if OBJECTS:
             extra["objects"], extra["objects_exclude"] = True, OBJECTS_EXCLUDE
+        if OBJECTS_VALUES is not None:
+            extra["objects_values"], extra["objects_values_name"] = OBJECTS_VALUES, OBJECTS_VALUES_NAME
+        if OBJECTS_CONFIDENCE:
+            extra["objects_confidence"] = True
         save_predictions(predict_model, predict_path, regression, merge, all_classes, specific_class, large_file, AOI, year,
                          validation_vision, class_zero, tta=TTA, **extra)
     print(f"Operation completed in {(time.time() - t0) / 60:.2f} minutes.")

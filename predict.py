@@ -67,7 +67,7 @@ from unet_amd.tta import parse as tta_codes
 from unet_amd.vectorize import check_vector, epsg_of_tags, vectorize_mask
 from unet_amd.instances import Instances, check_instances
 from unet_amd.zonal import check_zones, zonal_mask, zonal_plane
-from unet_amd.objects import check_objects, objects_mask
+from unet_amd.objects import check_object_planes, check_objects, objects_mask, read_value_raster
 
 
 def store_tif(output_file, data, geotrans=None, tags=None, nodata=None, class_zero=False, compress=None, predictor=1,
@@ -116,6 +116,8 @@ class OutputPlan:
     vector_simplify: Optional[float] = None
     instances: Optional[Instances] = None
     instances_raster: bool = False
+    objects_values: Optional[str] = None              # the column prefix of the value raster's statistics per object; None: no value raster
+    objects_confidence: bool = False                  # the objects file gains confidence_*: the merged probability of the chosen class
     zones: bool = False                               # a zonal table is written
     zonal_values: bool = False                        # ... of the float plane (zonal_plane) instead of the class mask (zonal_mask)
     zonal_objects: bool = False
@@ -159,11 +161,14 @@ class OutputPlan:
 def check_outputs(regression=False, all_classes=False, specific_class=None, large_file=False, merge=True, class_zero=False, blend="mean",
                   postprocess=None, compress=None, predictor=1, tile=None, overviews=None, vector=None, vector_exclude=None, vector_simplify=None,
                   instances=None, instances_raster=False, raster=True, return_array=True, raster_arg="instances_raster", *, zonal_values=False,
-                  objects=None, objects_exclude=None, zones=None, zonal_objects=False) -> OutputPlan:
+                  objects_values=None, objects_values_name="value", objects_confidence=False, objects=None, objects_exclude=None, zones=None,
+                  zonal_objects=False) -> OutputPlan:
     """Every check of the two entry points' output arguments, from the arguments alone and in one order -> the OutputPlan.  vector: vector= or
     vector_path=; instances_raster: whether the argument named raster_arg asks for the instance raster; raster: whether out_path is given;
     objects: objects= or objects_path=; zones: zones= or zones_path= (the entry points check that its output path is there); zonal_values:
-    the table summarises the one float plane of the output (regression, specific_class) instead of the class mask.  Everything from
+    the table summarises the one float plane of the output (regression, specific_class) instead of the class mask; objects_values:
+    objects_values= or objects_values_path=, the value raster whose statistics per object join the objects file as <objects_values_name>_*;
+    objects_confidence: the same of the merged probability of the chosen class, as confidence_*.  Everything from
     zonal_values on is passed by keyword, as both entry points always did, so that a new argument can never shift a positional one"""
     mode = OutputPlan(bool(regression), bool(all_classes), specific_class, bool(large_file), bool(merge), bool(class_zero), bool(raster))
     check_blend(blend, large_file, merge)
@@ -181,6 +186,7 @@ def check_outputs(regression=False, all_classes=False, specific_class=None, larg
     obj = check_objects(objects, objects_exclude, class_zero)
     if obj is not None:
         mode.needs_mask("object attributes", "measured")
+    values_name = check_object_planes(objects_values, objects_values_name, objects_confidence, obj is not None)
     inst = check_instances(instances)
     if inst is not None:
         mode.needs_mask("instances", "split")
@@ -195,16 +201,20 @@ def check_outputs(regression=False, all_classes=False, specific_class=None, larg
         raise ValueError("return_array=False needs out_path: the prediction would go nowhere")
     return dataclasses.replace(mode, blend=blend, postprocess=post, compress=compress, predictor=predictor, tile=tile, overviews=overviews,
                                vector=vec, vector_simplify=vector_simplify, instances=inst, instances_raster=bool(instances_raster),
-                               zones=zonal, zonal_values=bool(zonal_values), zonal_objects=bool(zonal_objects), objects=obj)
+                               zones=zonal, zonal_values=bool(zonal_values), zonal_objects=bool(zonal_objects), objects_values=values_name,
+                               objects_confidence=bool(objects_confidence), objects=obj)
 
 
 def _write_outputs(plan: OutputPlan, out, device, gt, tags, raster_path, vector_path, instances_path, class_names, timing, zones_path=None,
-                   zonal_path=None, objects_path=None):
+                   zonal_path=None, objects_path=None, object_planes=None):
     """Rank 0's output stage on the merged array `out` of _Merge.finish (a tensor under plan.keep, else a NumPy array): the instance split (its
     dense ids as a uint32 GeoTIFF with the mask's geo tags, by tiffio.write_tiff, so compress, predictor and tile apply to it as to the mask),
     the object attributes (of the instances where there are any, else of the components; a vector file written too carries them on its
     features), the vector file, the zonal table (its objects are the instances where there are any, else the components), the move to the host unless
-    the raster is encoded from the tensor, the raster.  Returns what the raster is written from."""
+    the raster is encoded from the tensor, the raster.  object_planes: None or {name: (float32 plane on the output's grid, nodata)} -- the value
+    raster and the confidence plane, whose statistics per object (objects.object_values, after measure_objects on the same mask and labels:
+    the instance labels where there are any) join the objects file and the polygon features; timing gains objects_values_seconds.  Returns
+    what the raster is written from."""
     labels = ids = None
     if plan.instances is not None:
         out = torch.as_tensor(out)
@@ -219,7 +229,10 @@ def _write_outputs(plan: OutputPlan, out, device, gt, tags, raster_path, vector_
     if plan.objects is not None:
         out = torch.as_tensor(out)
         out = (out if out.is_cuda else out.to(device)).contiguous()
-        attributes = objects_mask(out, objects_path, plan.objects, gt, epsg_of_tags(tags), class_names, plan.class_zero, labels, ids, timing)
+        more = {}
+        if object_planes:          # without planes: the call it was
+            more["values"] = {name: (torch.as_tensor(a).to(out.device).contiguous(), nd) for name, (a, nd) in object_planes.items()}
+        attributes = objects_mask(out, objects_path, plan.objects, gt, epsg_of_tags(tags), class_names, plan.class_zero, labels, ids, timing, **more)
     if plan.vector is not None:
         extra = {} if attributes is None else {"attributes": attributes}          # without objects: the call it was
         vectorize_mask(out, vector_path, plan.vector, gt, epsg_of_tags(tags), class_names, plan.class_zero, timing, plan.vector_simplify, labels, ids,
@@ -378,10 +391,15 @@ class _Merge:
             else:
                 ops.mosaic_accumulate_weighted(slab, self._profile(h), self._profile(w), self.mosaic, self.count, self.wsum, y0 - self.lo, x0)
 
-    def finish(self, want, postprocess=None, timing: Optional[dict] = None, keep: bool = False):
+    def finish(self, want, postprocess=None, timing: Optional[dict] = None, keep: bool = False, extra: Optional[dict] = None):
         """want: "argmax" | "all" | int class index.  Returns (on rank 0) the full-size numpy array, None elsewhere.  postprocess: a
         PostProcess applied to the assembled class mask on rank 0 (want == "argmax" only: check_outputs).  keep (OutputPlan.keep): the result
-        comes back as the tensor it was assembled in -- on the device with one rank or RCCL, on the host for the int8 merge and gloo"""
+        comes back as the tensor it was assembled in -- on the device with one rank or RCCL, on the host for the int8 merge and gloo.
+        extra: a dict that asks for the confidence plane (want == "argmax", no int8 merge: check_outputs) and receives it on rank 0 as
+        extra["confidence"], float32 [MH, MW] in the tensor it was assembled in: c[p] = the maximum over the classes of the finalised mosaic at
+        p -- the merged probability of the class that the argmax chose, before postprocess.  Every rank takes the plane of its own rows and
+        rank 0 assembles it behind the mask, as it does a specific_class plane.  A pixel that no window covered holds 0.0 there: the
+        finalisation divides only where the hit count is positive, so all classes keep the zero they started from (and the mask class 0)"""
         rows, MW, MH = self.hi - self.lo, self.plan.MW, self.plan.MH
         if self.int8:
             merged, counter = self.mosaic[:, :rows].cpu().numpy(), self.count[:, :rows].cpu().numpy()
@@ -396,10 +414,16 @@ class _Merge:
             elif rows > 0:
                 ops.mosaic_finalize_rows_weighted(self.mosaic, self.count, self.wsum, 0, rows, am, fill=-9999.0 if self.raw else None)
             part = am[:rows] if want == "argmax" else (self.mosaic[:, :rows] if want == "all" else self.mosaic[want, :rows])
+        conf = torch.amax(self.mosaic[:, :rows], dim=0) if extra is not None else None          # a maximum is exact
         if postprocess is None:
-            return self._gather_rows(part, want == "all", True) if keep else self._gather_rows(part, want == "all")
+            out = self._gather_rows(part, want == "all", True) if keep else self._gather_rows(part, want == "all")
+            if conf is not None:
+                extra["confidence"] = self._gather_rows(conf, False, True)
+            return out
         # one rank: the mask goes from the argmax to the filters on the device; N ranks: rank 0 uploads the assembled mask again
         full = part if self.world == 1 else self._gather_rows(part, False)
+        if conf is not None:
+            extra["confidence"] = self._gather_rows(conf, False, True)
         if full is None:
             return None
         t0 = time.perf_counter()
@@ -437,10 +461,11 @@ class _Merge:
 
 
 def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch, make_input: Callable, want, timing: Optional[dict] = None,
-               tta: Optional[Tuple[int, ...]] = None, blend: str = "mean", postprocess=None, keep: bool = False):
+               tta: Optional[Tuple[int, ...]] = None, blend: str = "mean", postprocess=None, keep: bool = False, extra: Optional[dict] = None):
     """make_input(first, n, n_pad) -> ops.WindowBatch of placements [first, first + n) padded to n_pad windows (so that every
     forward runs on ONE batch geometry and no second set of activation buffers is allocated).  tta: parsed codes -- every batch runs
-    len(tta) forwards of that same geometry, their mean takes the place of the softmax in the merge.  The rest: OutputPlan's values"""
+    len(tta) forwards of that same geometry, their mean takes the place of the softmax in the merge.  extra: _Merge.finish's.  The rest:
+    OutputPlan's values"""
     mg = _Merge(model, places, MH, MW, regression, int8_merge, rank, world, blend)
     t0 = time.perf_counter()
     batches = mg.plan.batches(rank, batch)
@@ -457,7 +482,7 @@ def _run_merge(model, places, MH, MW, regression, int8_merge, rank, world, batch
     mg.exchange()
     if timing is not None and not int8_merge and mg.hi > mg.lo:      # coverage of this rank's strip (before the division consumes nothing of it)
         timing.update(hits_min=int(mg.count.min().item()), hits_max=int(mg.count.max().item()))
-    out = mg.finish(want, postprocess, timing, keep)
+    out = mg.finish(want, postprocess, timing, keep, extra)
     if timing is not None:
         torch.cuda.synchronize()
         timing.update(seconds=time.perf_counter() - t0, windows_this_rank=sum(n for _, n in batches), windows=len(mg.plan.places),
@@ -508,7 +533,8 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                    batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
                    return_array: bool = True, tile=None, overviews=None, vector_path=None, vector_exclude=None, vector_simplify=None,
                    instances=None, instances_path=None, zones_path=None, zonal_path=None, zonal_objects: bool = False,
-                   objects_path=None, objects_exclude=None, zonal_values: bool = False):
+                   objects_path=None, objects_exclude=None, zonal_values: bool = False, objects_values_path=None, objects_values_name: str = "value",
+                   objects_confidence: bool = False):
     """Sliding-window prediction of a whole raster: equals split_raster(raster, patch_size=size, patch_overlap=overlap, max_empty) ->
     save_predictions(merge=True) on the tiles it writes (create_tiles_unet.py:252-434, predict.py:146-334).
 
@@ -578,6 +604,18 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
              (nodata -9999 is not a valid pixel) or specific_class -- as pixels, area, valid, mean, std, min, max and sum per zone, summed
              on the device in fixed point so that the table does not depend on scheduling (unet_amd/zonal.py); not for the class mask,
              all_classes, large_file or with zonal_objects (ValueError)
+    objects_values_path  None | the path of a one-band GeoTIFF on the OUTPUT's grid (needs objects_path): a canopy height model, an NDVI, a slope.
+             Every object gains <objects_values_name>_valid, _mean, _std, _sum, _min, _max and _peak_x, _peak_y, the centre of the pixel where
+             the value peaks (the treetop), summed on the device in fixed point (unet_amd/objects.py, object_values).  The raster must have
+             the output's height, width and six geotransform numbers exactly (ValueError names both grids; there is no resampling; where the
+             input is an array, so that the output has no georeference, the shape alone is compared); float32 is taken as it is, uint8, uint16
+             and int16 are converted (exactly), anything else is refused; nodata comes from the file.  Rank 0 reads it and uploads it once.
+             timing gains objects_values_seconds
+    objects_values_name  the prefix of those columns ("value"; e.g. "height")
+    objects_confidence  True (needs objects_path): every object gains confidence_valid, _mean, _std, _sum, _min, _max, _peak_x, _peak_y of the
+             merged probability of the class that the merge chose at each pixel -- the maximum over the classes of the finalised mosaic,
+             before postprocess (a pixel that postprocess moved to another class keeps the probability of the class it had; a pixel that no
+             window covered holds 0.0).  The plane exists only with this option
     Returns on rank 0 the merged array (uint8 argmax [H', W'] by default; float32 [C, H', W'] for all_classes; one float32 plane for
     specific_class / regression; int8 planes with large_file) where H' x W' is the extent of the kept windows, None on the other ranks;
     with out_path it is also written as a GeoTIFF (class_zero shifts the class ids back, predict.py:19-52)."""
@@ -587,7 +625,8 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
                          overviews, vector_path, vector_exclude, vector_simplify, instances, instances_raster=instances_path is not None,
                          raster=out_path is not None, return_array=return_array, raster_arg="instances_path", objects=objects_path,
                          objects_exclude=objects_exclude, zones=zones_path, zonal_objects=zonal_objects,
-                         zonal_values=zonal_values)
+                         zonal_values=zonal_values, objects_values=objects_values_path, objects_values_name=objects_values_name,
+                         objects_confidence=objects_confidence)
     model = getattr(model, "model", model)
     codes = tta_codes(tta, [(size, size)])
     rank, _, world = _dist_ctx()
@@ -621,17 +660,25 @@ def predict_raster(model, raster, size: int = 512, overlap: float = 0.2, *, max_
         raise ValueError("every window of the raster is emptier than max_empty: nothing to predict")
     places, MH, MW, oy, ox, rows = _raster_plan(wins, size, H, W, batch_size)
     gtab = ops.window_table(rows, dev)
+    ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
+    planes = {}
+    if plan.objects_values is not None and rank == 0:          # read and checked before the merge, uploaded once
+        values, values_nodata = read_value_raster(objects_values_path, (MH, MW), ogt)
+        planes[plan.objects_values] = (torch.from_numpy(values).to(dev), values_nodata)
 
     def make_input(first, n, n_pad):
         _check_batch(first, n, n_pad, len(rows))
         return ops.WindowBatch(src, gtab, first, n_pad, size, size)
 
+    more = {"extra": {}} if plan.objects_confidence else {}          # without the option: the call it was
     with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):
         out = _run_merge(model, places, MH, MW, plan.regression, plan.int8_merge, rank, world, batch_size, make_input, plan.want, timing, codes,
-                         plan.blend, plan.postprocess, plan.keep)
+                         plan.blend, plan.postprocess, plan.keep, **more)
     if rank == 0:
-        ogt = None if gt is None else [gt[0] + ox * gt[1], gt[1], 0.0, gt[3] + oy * gt[5], 0.0, gt[5]]
-        out = _write_outputs(plan, out, dev, ogt, tags, out_path, vector_path, instances_path, None, timing, zones_path, zonal_path, objects_path)
+        if plan.objects_confidence:
+            planes["confidence"] = (more["extra"]["confidence"], None)
+        out = _write_outputs(plan, out, dev, ogt, tags, out_path, vector_path, instances_path, None, timing, zones_path, zonal_path, objects_path,
+                             planes or None)
     if timing is not None:
         timing.update(kept_windows=len(wins), all_windows=int(len(keep)), mosaic=(MH, MW))
     if rank != 0 or not return_array:
@@ -792,7 +839,7 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
                      batch_invariant: bool = False, tta=None, blend: str = "mean", postprocess=None, compress=None, predictor: int = 1,
                      tile=None, overviews=None, vector: bool = False, vector_exclude=None, vector_simplify=None, instances=None,
                      instances_raster: bool = False, zones=None, zonal_objects: bool = False, objects: bool = False, objects_exclude=None,
-                     zonal_values: bool = False):
+                     zonal_values: bool = False, objects_values=None, objects_values_name: str = "value", objects_confidence: bool = False):
     """tta, blend, postprocess, compress / predictor, tile / overviews, vector_exclude, vector_simplify and instances are predict_raster's (see
     there); the ValueErrors of check_outputs come before the model is loaded.  What differs here: tta applies to merged and per-tile outputs
     alike; blend, postprocess, vector and instances need merge=True (per-tile outputs: no overlap to blend, not post-processed, polygonized, split).
@@ -805,11 +852,14 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     objects (predict_raster's objects_path, with objects_exclude): True writes <merged raster stem>_objects.geojson beside the merged raster,
     one Point feature per object with its attributes and the class names of the vocab; it counts as an output of instances.
     zonal_values (predict_raster's, needs zones and merge=True): <merged raster stem>_zonal.geojson holds the statistics of the float plane.
+    objects_values (predict_raster's objects_values_path: the path of the value raster, on the merged raster's grid), objects_values_name and
+    objects_confidence need objects=True; the columns join <merged raster stem>_objects.geojson and, with vector=True, the polygon features.
     validation_vision is accepted and ignored: the per-tile majority-class confusion plots (predict.py:56-143) are reporting, out of scope"""
     plan = check_outputs(regression, all_classes, specific_class, large_file, merge, class_zero, blend, postprocess, compress, predictor, tile,
                          overviews, vector or None, vector_exclude, vector_simplify, instances, instances_raster, objects=objects or None,
                          objects_exclude=objects_exclude, zones=zones, zonal_objects=zonal_objects,
-                         zonal_values=zonal_values)
+                         zonal_values=zonal_values, objects_values=objects_values, objects_values_name=objects_values_name,
+                         objects_confidence=objects_confidence)
     rank, local_rank, world = _dist_ctx()
     learn = load_learner(Path(predict_model), device=f"cuda:{local_rank}" if world > 1 else "cuda")
     model = learn.model
@@ -826,7 +876,8 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     t_start = time.perf_counter()
     windows = _tile_windows(batch_size, model._device, learn.dls.train_ds.dtype == "int16")
     if merge:
-        out, gt = _save_merged(model, tiles, geos, windows, rank, world, plan, batch_size, batch_invariant, codes, timing)
+        extra = {} if plan.objects_confidence else None
+        out, gt = _save_merged(model, tiles, geos, windows, rank, world, plan, batch_size, batch_invariant, codes, timing, extra)
     else:
         _save_tiles(model, tiles, geos, windows, rank, world, output_folder, plan, batch_size, batch_invariant, codes)
         if world > 1:
@@ -842,19 +893,25 @@ def save_predictions(predict_model, predict_path, regression, merge=False, all_c
     name = "_".join(filter(None, [AOI, year, model_name, "prediction"])) + ".tif"
     vocab = getattr(learn.dls, "vocab", None) if plan.vector is not None or plan.zones or plan.objects is not None else None
     names = list(vocab) if vocab is not None and len(vocab) >= model.n_out else None
+    planes = {}
+    if plan.objects_values is not None:
+        values, values_nodata = read_value_raster(objects_values, tuple(out.shape), gt)
+        planes[plan.objects_values] = (torch.from_numpy(values).to(model._device), values_nodata)
+    if plan.objects_confidence:
+        planes["confidence"] = (extra["confidence"], None)
     _write_outputs(plan, out, model._device, gt, geos[0][1], output_folder / name, (output_folder / name).with_suffix(".geojson"),
                    output_folder / (Path(name).stem + "_instances.tif") if plan.instances_raster else None, names, timing,
                    zones, output_folder / (Path(name).stem + "_zonal.geojson") if plan.zones else None,
-                   output_folder / (Path(name).stem + "_objects.geojson") if plan.objects is not None else None)
+                   output_folder / (Path(name).stem + "_objects.geojson") if plan.objects is not None else None, planes or None)
     print(f"Prediction stored in {output_folder}.")
     return output_folder if regression else output_folder / name
 
 
-def _save_merged(model, tiles, geos, windows: Callable, rank, world, plan: OutputPlan, batch_size, batch_invariant, codes, timing):
+def _save_merged(model, tiles, geos, windows: Callable, rank, world, plan: OutputPlan, batch_size, batch_invariant, codes, timing, extra=None):
     """overlap merge (predict.py:257-355) of this rank's share of the tiles -> (merged array on rank 0, None elsewhere; geotransform of
     the mosaic).  The extent follows from the tiles' geotransforms and sizes, which are known from the headers BEFORE any tile is
     predicted: every batch is accumulated into the device mosaic as soon as it is computed and its probabilities are dropped (the
-    reference keeps all tiles' probabilities until the end)."""
+    reference keeps all tiles' probabilities until the end).  extra: _Merge.finish's."""
     if any(g[0] is None for g in geos):
         raise ValueError("merge=True needs georeferenced tiles (.npy tiles carry no geotransform)")
     gts = np.array([[g[0][0], g[3], g[0][1], g[0][3], g[2], g[0][5]] for g in geos], dtype=np.float64)
@@ -883,8 +940,9 @@ def _save_merged(model, tiles, geos, windows: Callable, rank, world, plan: Outpu
             return windows(d, n)
 
         with (ops.tuning(plan_batch=1) if batch_invariant else contextlib.nullcontext()):          # (see predict_raster)
+            more = {} if extra is None else {"extra": extra}          # without the option: the call it was
             out = _run_merge(model, places, MH, MW, plan.regression, plan.int8_merge, rank, world, batch_size, make_input, plan.want, timing, codes,
-                         plan.blend, plan.postprocess, plan.keep)
+                         plan.blend, plan.postprocess, plan.keep, **more)
     return out, [ulx_full, xres, 0.0, uly_full, 0.0, yres]
 
 

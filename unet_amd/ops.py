@@ -2190,6 +2190,44 @@ def obj_point(mask: torch.Tensor, labels: torch.Tensor, offs: torch.Tensor, excl
                              key64.data_ptr(), point.data_ptr(), _stream()), what)
 
 
+# ---------------------------------------------------------------------------------------------- float statistics per object (csrc/object_values.hip)
+
+def obj_absmax(mask: torch.Tensor, values: torch.Tensor, exclude, nodata, absmax: torch.Tensor):
+    """absmax (int64[1], reset) = the largest bit pattern of |values| over the valid pixels: class not excluded, value finite and not nodata"""
+    what = "obj_absmax"
+    H, W = check_objects_shape(what, mask.shape if isinstance(mask, torch.Tensor) else ())
+    has, nd = check_zonal_nodata(what, nodata)
+    _table_tensor(what, "mask", mask, torch.uint8, (H, W))
+    _table_tensor(what, "values", values, torch.float32, (H, W))
+    _table_tensor(what, "absmax", absmax, torch.int64, (1,))
+    _on_one_device(what, [("mask", mask), ("values", values), ("absmax", absmax)])
+    words = (C.c_uint32 * 8)(*vec_exclude_words(exclude))
+    check(lib.unet_obj_absmax(mask.data_ptr(), values.data_ptr(), H, W, words, has, nd, absmax.data_ptr(), _stream()), what)
+
+
+def obj_values(mask: torch.Tensor, labels: torch.Tensor, values: torch.Tensor, offs: torch.Tensor, exclude, P: int, nodata, shift: int,
+               table: Optional[torch.Tensor], bad: torch.Tensor):
+    """table (int64 [6, P], initialised by the call): valid, sum_q, sq_lo, sq_hi of the P objects whose index is offs[anchor] under
+    q = rint(double(v) * 2^shift), then min and max as one word each: the float32 bits in the low half, the int32 linear index of the first
+    pixel that attains it in the high half (+inf / -inf and -1 without a valid pixel).  bad (int64[1]) is reset and gains the three bits of
+    obj_accumulate and bit 3 for a valid pixel with |q| > 2^30 (unet_hip.h).  P = 0 (table None): the check of the input alone"""
+    what = "obj_values"
+    H, W = _obj_planes(what, mask, labels, offs)
+    _obj_count(what, P, H * W, 0)
+    has, nd = check_zonal_nodata(what, nodata)
+    check_zonal_shift(what, shift)
+    _table_tensor(what, "values", values, torch.float32, (H, W))
+    _table_tensor(what, "bad", bad, torch.int64, (1,))
+    if P:
+        _table_tensor(what, "table", table, torch.int64, (6, P))
+    elif table is not None:
+        raise ValueError(f"{what}: no table without objects")
+    _on_one_device(what, [("mask", mask), ("labels", labels), ("values", values), ("offs", offs), ("table", table), ("bad", bad)])
+    words = (C.c_uint32 * 8)(*vec_exclude_words(exclude))
+    check(lib.unet_obj_values(mask.data_ptr(), labels.data_ptr(), values.data_ptr(), offs.data_ptr(), H, W, words, P, has, nd, shift, _p(table),
+                              bad.data_ptr(), _stream()), what)
+
+
 # ---------------------------------------------------------------------------------------------- GeoTIFF strips on the device (csrc/tiff_encode.hip)
 
 def tiff_lzw_cap(n: int) -> int:

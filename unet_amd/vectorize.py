@@ -456,6 +456,8 @@ def check_geojson_args(geotransform=None, epsg=None):
 
 
 ATTRIBUTE_KEYS = ("perimeter", "centroid_x", "centroid_y", "diameter", "compactness", "on_edge", "point_x", "point_y")
+# the other keys of a row of object_rows(values=None): a feature has them already, or (bbox) the geometry says it
+_OWN_ROW_KEYS = frozenset(ATTRIBUTE_KEYS + ("class", "name", "pixels", "area", "bbox", "instance"))
 
 
 def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, codes=None, class_zero: bool = False, instance=None,
@@ -467,7 +469,8 @@ def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, co
     the legacy "crs" member names urn:ogc:def:crs:EPSG::<code>.  instance: None, or one id per polygon, written as the property `instance`
     behind the others.  attributes: None, or a mapping from a polygon's label to its row of unet_amd/objects.object_rows; a feature whose label
     has a row gains the ATTRIBUTE_KEYS of that row behind its other properties (joined by label: with a simplification some polygons get
-    no feature).  Returns the number of features.  Host code."""
+    no feature), and behind them whatever the row holds beyond the keys of object_rows itself: the <name>_* columns of
+    object_rows(values=).  Returns the number of features.  Host code."""
     check_geojson_args(geotransform, epsg)
     a = _host_arrays(polys)
     labels = a["poly_label"].tolist() if attributes is not None else None
@@ -499,6 +502,7 @@ def write_geojson(path, polys, geotransform=None, epsg: Optional[int] = None, co
         row = attributes.get(labels[i]) if attributes is not None else None
         if row is not None:
             props.update((k, row[k]) for k in ATTRIBUTE_KEYS)
+            props.update((k, v) for k, v in row.items() if k not in _OWN_ROW_KEYS)
         coords = ",".join("[" + ",".join(pts[rs[r]:rs[r + 1]] + pts[rs[r]:rs[r] + 1]) + "]" for r in rings[prs[i]:prs[i + 1]])
         feats.append('{"type":"Feature","properties":' + json.dumps(props) + ',"geometry":{"type":"Polygon","coordinates":[' + coords + "]}}")
     head = '{"type":"FeatureCollection",'

@@ -50,8 +50,8 @@ Accuracy    |q * 2^-s - v| <= 2^(E-31) for every valid pixel, so the mean differ
 Bad input   a zone outside -1 .. Z - 1 is counted nowhere, indexes nothing and raises ValueError after the launch, as in zonal_counts.
 
 write_zonal and read_zones are host code on the json and csv modules.  Out of scope: several float planes at once (all_classes), median,
-percentiles and histograms, weighted or fractional pixel coverage, float64 and integer value planes, per-object float statistics (pass dense
-object ids as the zone plane), overlapping zones counted more than once, ALL_TOUCHED, line and point zones, reprojection, Shapefile and
+percentiles and histograms, weighted or fractional pixel coverage, float64 and integer value planes, per-object float statistics (objects.object_values
+has them), overlapping zones counted more than once, ALL_TOUCHED, line and point zones, reprojection, Shapefile and
 GeoPackage, per-tile outputs, tables accumulated across ranks (the stage runs on rank 0's assembled output, as the vector stage does), and a
 host fallback (without a device the device calls raise)."""
 from __future__ import annotations
